@@ -8,6 +8,8 @@ rank per GPU over RCCL; rendezvous comes from RANK/LOCAL_RANK/WORLD_SIZE/
 MASTER_* env vars. W untimed warmup steps, then EXACTLY K timed steps
 bracketed by barrier + torch.cuda.synchronize on both sides; elapsed is the
 MAX over ranks; rank 0 prints ONE JSON line.
+    --dump-outputs DIR  write the last timed step's output to DIR/out.npy
+    --full              measurements beyond the headline figure (none today)
 
 Metric (BASELINE.json): attention tokens/sec at B=1, H=32, d=128, bf16 —
 the decode step attends one query over the whole sharded KV sequence, so
@@ -53,7 +55,37 @@ def parse_args(argv=None):
     p.add_argument("--combine", type=str, default="auto")
     p.add_argument("--profile", type=str, default=None, metavar="DIR",
                    help="export a torch.profiler chrome trace of a few steps")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's "
+                        "output to DIR/out.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none today: a plain run already does only "
+                        "setup, warmup, the timed steps and the result line)")
     return p.parse_args(argv)
+
+
+# --dump-outputs budget: 64 MB in all; larger outputs are sampled
+_DUMP_MAX_ELEMS = (64 << 20) // 4
+_DUMP_SAMPLE_ELEMS = 4 << 20
+
+
+def dump_outputs(out: torch.Tensor, dump_dir: str) -> None:
+    """Write what the timed path returned to its caller as DIR/out.npy
+    (float32). Inputs are seeded (data.make_data), so two builds run with
+    the same arguments can be compared output for output. An output over the
+    64 MB budget is reduced to a fixed, seeded sample of its elements."""
+    import numpy as np
+
+    flat = out.detach().float().reshape(-1).cpu()
+    if flat.numel() > _DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(flat.numel(), (_DUMP_SAMPLE_ELEMS,), generator=g)
+        arr = flat[idx].numpy()
+    else:
+        arr = flat.numpy().reshape(tuple(out.shape))
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "out.npy"), arr)
 
 
 def run(rank: int, world: int, args) -> None:
@@ -105,8 +137,12 @@ def run(rank: int, world: int, args) -> None:
             prof.export_chrome_trace(os.path.join(args.profile, "bench_trace.json"))
         with StepTimer(device) as t:
             for _ in range(args.steps):
-                step()
+                out = step()
         elapsed = t.max_over_ranks()
+
+        if args.dump_outputs and rank == 0:
+            # the combined result is replicated on every rank: rank 0 writes
+            dump_outputs(out, args.dump_outputs)
 
         if rank == 0:
             seq_total = args.seq_per_gpu * world

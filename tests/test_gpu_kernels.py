@@ -490,7 +490,11 @@ def test_experimental_prefill_variants(ext, flag, val):
         "    torch.testing.assert_close(l.cpu(), rl, rtol=1e-3, atol=1e-3)\n"
         "print('VARIANT_OK')\n"
     )
+    # the child imports the in-tree package whatever directory pytest runs from
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, **{flag: val})
+    env["PYTHONPATH"] = os.pathsep.join(
+        p for p in (repo, os.environ.get("PYTHONPATH")) if p)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True,
                        text=True, env=env, timeout=300)
     assert r.returncode == 0 and "VARIANT_OK" in r.stdout, r.stdout + r.stderr

@@ -130,12 +130,15 @@ def test_half_precision_inputs_close_to_fp32():
 
 def test_driver_main_cpu(monkeypatch, tmp_path):
     """Reference-parity driver main() runs end-to-end on CPU (model.py:129)."""
-    import os
-
-    os.chdir(tmp_path)
+    monkeypatch.chdir(tmp_path)
+    from tree_attention_torch_amd import main as driver
     from tree_attention_torch_amd.config import TreeAttentionConfig
     from tree_attention_torch_amd.main import main
 
+    # the CPU path is what this test is about: pin it, so that a machine
+    # with a GPU does not route the fp32 workload to the bf16/fp16 kernels
+    monkeypatch.setattr(driver, "local_device",
+                        lambda rank=None: torch.device("cpu"))
     cfg = TreeAttentionConfig(seq_len=256, num_heads=2, head_dim=64,
                               dtype="fp32", warmup=1, steps=2)
     main(0, 1, cfg)  # should not raise
