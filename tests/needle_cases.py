@@ -1,0 +1,677 @@
+"""Needle inputs: attention problems whose answer names the key that was read.
+
+On ``randn`` Q/K/V the softmax is close to uniform over hundreds of keys, so
+one key more or less, or two V rows exchanged, moves ``out`` and ``lse`` by
+less than the suite's bars (docs/NEEDLE_TESTS.md has the table). Here every
+query row is ``2 * K[target]``: with D=128 and scale 1/sqrt(D) the target
+scores ~22.6, every other key ~N(0, 2), so ``out ~= V[target]`` (|.| up to ~4)
+and ``lse ~= 22.6``. Reading the wrong key, or not reading the right one,
+moves the answer by O(1).
+
+This module is a plain helper (not a conftest). It holds
+
+* the needle builders and the shared CASE TABLE,
+* an fp64 naive attention that can be MUTATED (the errors the suite must see),
+* ``guarded``: K/V views with decoy-K / NaN-V rows on both sides,
+* ``compare``: the project's existing bars, used by BOTH the CPU sensitivity
+  tests (tests/test_needle_sensitivity.py) and the GPU tests
+  (tests/test_gpu_needles.py), so what is proven on the CPU is what runs on
+  the GPU,
+* the GPU runners (shared with the env-variant child processes).
+"""
+
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from functools import lru_cache
+
+import torch
+
+SEED = 20260920
+CACHE_CAP = 1024
+GUARD_PRE, GUARD_POST = 2, 130  # > one 128-key tile of rows behind the view
+
+_TD = {"bf16": torch.bfloat16, "fp16": torch.float16,
+       "fp8": torch.float8_e4m3fn}
+
+# (out bar, lse bar), rtol = atol, exactly the bars the suite already uses:
+# half  - tests/test_gpu_kernels.py::_check_decode / _check_fp16
+# fp8   - _check_fp8_decode (measured worst 0.0155 / 0.0213, x2.5)
+# mx_*  - test_mx_decode_vs_oracle (tame-data branches, hw and dequant)
+BARS = {
+    "half": (2.5e-2, 1e-3),
+    "fp8": (4e-2, 5e-2),
+    "mx_hw": (4e-2, 3e-2),
+    "mx_dequant": (2e-2, 1e-2),
+}
+
+PREFILL_ROUTES = ("prefill", "prefill_d64", "prefill_fp8", "prefill_mx")
+CAUSAL_FAMILIES = ("diag", "first_masked", "below")
+
+
+# --------------------------------------------------------------------------
+# case table
+# --------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Case:
+    route: str      # which entry point / kernel (see run_kernel)
+    dtype: str      # bf16 | fp16 | fp8 | mx
+    hq: int
+    hkv: int
+    tkv: int
+    tq: int
+    families: tuple
+    seams: tuple = ()      # key indices s where a tile/sub-block/split begins
+    d: int = 128
+    q_offset: int = -1     # -1: tkv - tq - 3 (three hidden keys at the end)
+    guard: bool = False    # GPU also runs it on guarded K/V (B=1, Hkv=1)
+    cuts: tuple = ()       # sharded routes: shard boundaries
+    note: str = ""
+
+    @property
+    def qoff(self) -> int:
+        return max(self.tkv - self.tq - 3, 0) if self.q_offset < 0 \
+            else self.q_offset
+
+    @property
+    def kind(self) -> str:
+        if self.route == "mx_dequant":
+            return "mx_dequant"
+        if self.dtype == "mx":
+            return "mx_hw"
+        return "fp8" if self.dtype == "fp8" else "half"
+
+    @property
+    def id(self) -> str:
+        s = (f"{self.route}-{self.dtype}-h{self.hq}kv{self.hkv}-t{self.tkv}"
+             f"q{self.tq}")
+        if self.d != 128:
+            s += f"-d{self.d}"
+        if self.q_offset >= 0:
+            s += f"-qo{self.q_offset}"
+        if self.seams:
+            sm = ".".join(map(str, self.seams[:4]))
+            s += f"-seams{sm}" + ("+" if len(self.seams) > 4 else "")
+        return s
+
+
+def split_chunk(b: int, hkv: int, tkv: int) -> int:
+    """Keys per split of the split-KV decode kernels. Mirrors the binding's
+    split heuristic for tkv <= 1024 (at most two splits, chunk a multiple of
+    128); used only to NAME the split seam a case targets."""
+    max_s = -(-tkv // 512)
+    bh = b * hkv
+    s = 512 // bh if 512 % bh == 0 else -(-768 // bh)
+    s = max(1, min(s, max_s))
+    return (-(-tkv // s) + 127) // 128 * 128
+
+
+def pick_seams(tkv: int, tile: int, rows: int, chunk: int = 0,
+               sub: int = 0) -> tuple:
+    """Seams of a kernel over tkv keys, most important first (split seams,
+    then tile seams from both ends inwards, then sub-block seams), cut so
+    that {0, tkv-1} plus both sides of every seam fit into `rows` targets."""
+    out: list[int] = []
+
+    def add(xs):
+        for x in xs:
+            if 0 < x < tkv and x not in out:
+                out.append(x)
+
+    if chunk:
+        add(range(chunk, tkv, chunk))
+    tiles = list(range(tile, tkv, tile))
+    inter = []
+    while tiles:
+        inter.append(tiles.pop())       # last seam first: the tail tile
+        if tiles:
+            inter.append(tiles.pop(0))
+    add(inter)
+    if sub:
+        add(range(sub, tkv, sub))
+    return tuple(out[: max((rows - 2) // 2, 0)])
+
+
+def seam_targets(case: Case) -> list[int]:
+    t = case.tkv
+    cand = [0, t - 1]
+    for s in case.seams:
+        cand += [s - 1, s]
+    seen, out = set(), []
+    for c in cand:
+        if 0 <= c < t and c not in seen:
+            seen.add(c)
+            out.append(c)
+    assert len(out) <= case.hq * case.tq, \
+        f"{case.id}: {len(out)} seam targets do not fit the query rows"
+    return out
+
+
+def _decode_family(tkv: int, tq: int) -> tuple:
+    if tkv - tq < 1:   # no hidden key can exist: first_masked impossible
+        return ("seam", "diag")
+    return ("seam", "diag", "first_masked")
+
+
+def _build_table() -> list[Case]:
+    cases: list[Case] = []
+
+    def add(route, dtype, hq, hkv, tkv, tq, tile, *, d=128, sub=0, guard=False,
+            chunk=True, families=None, q_offset=-1, cuts=(), note=""):
+        ch = split_chunk(1, hkv, tkv) if chunk else 0
+        seams = pick_seams(tkv, tile, hq * tq, ch, sub)
+        if cuts:
+            seams = tuple(dict.fromkeys(tuple(cuts[1:-1]) + seams))[
+                : (hq * tq - 2) // 2]
+        fam = families or _decode_family(tkv, tq)
+        cases.append(Case(route, dtype, hq, hkv, tkv, tq, fam, seams, d,
+                          q_offset, guard and hkv == 1, tuple(cuts), note))
+
+    # -- bf16/fp16 split-KV decode (fa_fwd_kernel): 64-key tiles, chunk a
+    #    multiple of 128, second split above 512 keys (513 -> 384 + 129)
+    for tkv in (1, 63, 64, 65, 513, 1000):
+        add("decode", "bf16", 32, 32, tkv, 1, 64)               # G=1
+        add("decode", "bf16", 16, 1, tkv, 1, 64, guard=True)    # G=16, Tq=1
+        add("decode", "bf16", 8, 2, tkv, min(4, tkv), 64)       # G=4, Tq=4
+        add("decode", "bf16", 4, 1, tkv, min(4, tkv), 64, guard=True)
+    # G=2, Tq=8 causal, frontier ACROSS the split seam (384) of Tkv=513:
+    # rows 380..383 leave the second split all-masked (lse_part = -inf)
+    add("decode", "bf16", 2, 1, 513, 8, 64, guard=True, q_offset=380,
+        note="frontier across split seam")
+    add("decode", "fp16", 8, 2, 513, 4, 64)
+    add("decode", "fp16", 16, 1, 1000, 1, 64, guard=True)
+    add("decode", "fp16", 2, 1, 513, 8, 64, guard=True, q_offset=380)
+
+    # -- other decode kernels: the same seam set on their 128-key tile
+    for tkv in (1, 127, 128, 129, 513, 1000):
+        add("decode_fp8", "fp8", 8, 2, tkv, min(4, tkv), 128)
+        add("decode_fp8", "fp8", 16, 1, tkv, 1, 128, guard=True)
+        add("decode_d64", "bf16", 8, 2, tkv, min(4, tkv), 128, d=64)
+        for d in (32, 112):
+            add("decode_narrow", "bf16", 8, 2, tkv, min(4, tkv), 128, d=d)
+    add("decode_fp8", "fp8", 2, 1, 513, 8, 128, guard=True, q_offset=380)
+    add("decode_d64", "fp16", 16, 1, 513, 1, 128, d=64, guard=True)
+    for route in ("mx_hw", "mx_dequant"):
+        for tkv in (64, 576):
+            add(route, "mx", 8, 2, tkv, 4, 64)
+            add(route, "mx", 16, 1, tkv, 1, 64)
+        add(route, "mx", 2, 1, 576, 8, 64, q_offset=380)
+        # causal frontier 17..32 and 81..96 keys into a 128-key tile: the
+        # tail already reads block 1 of a V-scale window (interleaved 16s)
+        add(route, "mx", 16, 1, 576, 1, 64, q_offset=535)   # tile 512: 24
+        add(route, "mx", 8, 2, 576, 4, 64, q_offset=210)    # tile 128: 86
+
+    # -- looped spec-decode route through local_attention
+    add("spec", "bf16", 4, 4, 600, 17, 64)
+    add("spec", "bf16", 8, 4, 600, 24, 64)
+
+    # -- zero-copy cache kernel: cap 1024 (two 512-key splits), live length
+    #    from device memory, guard pattern behind the live prefix
+    for dt, tile in (("bf16", 64), ("fp8", 128)):
+        for live in (1, 64, 65, 511, 512, 513, 1023, 1024):
+            seams = pick_seams(live, tile, 32, 512)
+            cases.append(Case("cache", dt, 8, 2, live, min(4, live),
+                              ("seam",), seams))
+
+    # -- prefill: 256-row q-blocks, 32-row waves, 128-key tiles, 32/64-key
+    #    sub-blocks. ext.flash_attention is called directly: local_attention
+    #    would loop the decode kernel at these sizes.
+    pf = ("diag", "first_masked", "seam", "below")
+    shapes = ((33, 36, -1), (257, 260, -1), (256, 384, 61), (300, 303, -1))
+    for tq, tkv, qo in shapes:
+        add("prefill", "bf16", 2, 2, tkv, tq, 128, sub=32, chunk=False,
+            families=pf, q_offset=qo)
+        add("prefill", "bf16", 4, 1, tkv, tq, 128, sub=32, chunk=False,
+            families=pf, q_offset=qo, guard=True)          # GQA 4:1
+        add("prefill", "fp16", 4, 1, tkv, tq, 128, sub=32, chunk=False,
+            families=pf, q_offset=qo, guard=True)
+        add("prefill_d64", "bf16", 4, 1, tkv, tq, 128, sub=32, chunk=False,
+            families=pf, q_offset=qo, guard=True, d=64)
+        add("prefill_fp8", "fp8", 4, 1, tkv, tq, 128, sub=32, chunk=False,
+            families=pf, q_offset=qo, guard=True)
+    for tq, tkv, qo in ((33, 64, -1), (257, 320, -1), (256, 384, 61),
+                        (300, 320, -1)):
+        add("prefill_mx", "mx", 4, 1, tkv, tq, 128, sub=32, chunk=False,
+            families=pf, q_offset=qo)
+    # (300, 320) leaves a 17-key tail under the first q-block's frontier;
+    # this one an 84-key tail (V-scale window 1, block 1, without 96 keys)
+    add("prefill_mx", "mx", 4, 1, 256, 100, 128, sub=32, chunk=False,
+        families=pf, q_offset=112)
+
+    # -- ranks emulated on one GPU: uneven cuts that are no tile multiples
+    cuts = (0, 65, 193, 300)
+    sf = ("seam", "diag", "first_masked")
+    add("sharded", "bf16", 8, 8, 300, 1, 64, cuts=cuts, families=sf,
+        q_offset=192, chunk=False)
+    add("sharded", "bf16", 8, 2, 300, 4, 64, cuts=cuts, families=sf,
+        q_offset=190, chunk=False)
+    add("sharded", "bf16", 8, 4, 300, 300, 128, cuts=cuts, families=sf,
+        q_offset=0, chunk=False, sub=32)
+    mcuts = (0, 64, 192, 320)
+    add("sharded_mx", "mx", 8, 8, 320, 1, 64, cuts=mcuts, families=sf,
+        q_offset=191, chunk=False)
+    add("sharded_mx", "mx", 8, 2, 320, 4, 64, cuts=mcuts, families=sf,
+        q_offset=189, chunk=False)
+    add("sharded_mx", "mx", 8, 4, 320, 300, 128, cuts=mcuts, families=sf,
+        q_offset=0, chunk=False, sub=32)
+    ids = [c.id for c in cases]
+    assert len(set(ids)) == len(ids), "duplicate case ids"
+    return cases
+
+
+CASES = _build_table()
+
+
+# --------------------------------------------------------------------------
+# needle builders
+# --------------------------------------------------------------------------
+@dataclass
+class Needle:
+    case: Case
+    family: str
+    causal: bool
+    q_offset: int
+    kv_offset: int
+    scale: float
+    targets: torch.Tensor      # (Hq, Tq) local key index each row attends
+    q: torch.Tensor            # storage dtype (bf16/fp16), CPU
+    k: torch.Tensor | None     # storage dtype; None for MX
+    v: torch.Tensor | None
+    mx: tuple | None           # (k8, ks, v8, vs) for MX
+    ref_q: torch.Tensor        # fp32 views the oracle sees
+    ref_k: torch.Tensor
+    ref_v: torch.Tensor
+
+
+def family_targets(case: Case, family: str) -> torch.Tensor:
+    hq, tq, t = case.hq, case.tq, case.tkv
+    pos = (case.qoff + torch.arange(tq))[None, :].expand(hq, tq)
+    if family == "diag":
+        tg = pos.clone()
+    elif family == "first_masked":
+        # a row whose first hidden key would lie past the KV keeps its diag
+        tg = torch.where(pos + 1 < t, pos + 1, pos)
+    elif family in ("seam", "below"):
+        cand = seam_targets(case)
+        tg = torch.empty(hq, tq, dtype=torch.long)
+        for h in range(hq):
+            for r in range(tq):
+                c = cand if family == "seam" else \
+                    [x for x in cand if x <= case.qoff + r]
+                # shift by one after every full cycle, so that the map is
+                # not symmetric under a (head, row) transposition
+                j = h * tq + r
+                tg[h, r] = c[(j + j // len(c)) % len(c)]
+    else:
+        raise ValueError(family)
+    assert int(tg.min()) >= 0 and int(tg.max()) < t, (case.id, family)
+    return tg
+
+
+@lru_cache(maxsize=None)
+def _kv(case: Case):
+    """K/V for a case: randn rounded to the case's dtype, fixed seed. Shared
+    (and left unchanged) between the families and tests of one case."""
+    from tree_attention_torch_amd.quant import (dequantize_k_mx,
+                                                dequantize_v_mx,
+                                                quantize_k_mx, quantize_v_mx)
+
+    g = torch.Generator().manual_seed(SEED + case.tkv * 7 + case.hkv)
+    k = torch.randn(1, case.hkv, case.tkv, case.d, generator=g)
+    v = torch.randn(1, case.hkv, case.tkv, case.d, generator=g)
+    if case.dtype == "mx":
+        k8, ks = quantize_k_mx(k)
+        v8, vs = quantize_v_mx(v)
+        return None, None, (k8, ks, v8, vs), \
+            dequantize_k_mx(k8, ks), dequantize_v_mx(v8, vs)
+    ks_, vs_ = k.to(_TD[case.dtype]), v.to(_TD[case.dtype])
+    return ks_, vs_, None, ks_.float(), vs_.float()
+
+
+def needle_gain(d: int) -> float:
+    """q = gain * K[target]. The target scores gain*|k|^2/sqrt(D), any other
+    key gain*|k|*N(0,1)/sqrt(D), so the target leads the largest of ~1000
+    others (z ~ 3.3) by gain*(sqrt(D) - 3.3) nats: 16 at D=128 with gain 2.
+    Narrow heads need gain 4 for the same lead (D=32: 9.4, D=64: 18.8). A
+    power of two keeps the product exact in every dtype."""
+    return 2.0 if d >= 112 else 4.0
+
+
+@lru_cache(maxsize=None)
+def build(case: Case, family: str) -> Needle:
+    k, v, mx, kf, vf = _kv(case)
+    tg = family_targets(case, family)
+    g = case.hq // case.hkv
+    kvh = torch.arange(case.hq) // g
+    gain = needle_gain(case.d)
+    qf = gain * kf[:, kvh[:, None], tg]          # (1, Hq, Tq, D)
+    qdt = torch.float16 if case.dtype == "fp16" else torch.bfloat16
+    q = qf.to(qdt)
+    assert torch.equal(q.float(), qf), "gain*K must be exact in the query dtype"
+    if family == "first_masked" and case.kind in ("fp8", "mx_hw"):
+        # ANCHORED first-masked for the kernels that quantize P to e4m3: a
+        # query on a hidden key alone leaves a diffuse softmax over the
+        # visible keys, and e4m3's 2^-4 relative step on a p ~ 0.5 is
+        # 0.06 * |v| ~ 0.1 of output error - past the 4e-2 bar by the
+        # format's own precision. Adding the diagonal key keeps the correct
+        # answer one-hot (p = 1 is exact in e4m3): q = 4 K[pos] + 6 K[pos+1].
+        # The diagonal scores ~45 against N(0, 7.2^2) others; the hidden key
+        # would score ~68, so a mask that admits it hands it the row (dO =
+        # |V[pos] - V[pos+1]|, dLSE ~ 22). The sum rounds to the query
+        # dtype; the oracle reads the rounded query. Both properties are
+        # proven per row of the table in tests/test_needle_sensitivity.py.
+        pos = (case.qoff + torch.arange(case.tq))[None, :].expand_as(tg)
+        hidden = (tg != pos)[None, :, :, None]
+        q = torch.where(hidden, 3.0 * qf + 4.0 * kf[:, kvh[:, None], pos],
+                        qf).to(qdt)
+    if case.kind == "mx_hw":
+        ref_q = q.float().to(torch.float8_e4m3fn).float()  # in-kernel e4m3 Q
+        ref_k, ref_v = kf, vf
+    elif case.kind == "mx_dequant":
+        ref_q, ref_k, ref_v = q.float(), kf.bfloat16().float(), \
+            vf.bfloat16().float()
+    else:
+        ref_q, ref_k, ref_v = q.float(), kf, vf
+    causal = family in CAUSAL_FAMILIES
+    return Needle(case, family, causal, case.qoff if causal else 0, 0,
+                  1.0 / math.sqrt(case.d), tg, q, k, v, mx, ref_q, ref_k,
+                  ref_v)
+
+
+def guard_rows(nd: Needle, n: int):
+    """n guard rows per KV head: decoy K = 4 * (direction of a query of that
+    head's group, rotating over its rows) and V = NaN. A kernel that admits
+    one gives it ~4x the target's score and a NaN output; one that merely
+    multiplies it by p = 0 still gets NaN."""
+    c = nd.case
+    g = c.hq // c.hkv
+    j = torch.arange(n)
+    heads = torch.arange(c.hkv)[:, None] * g + (j % g)[None, :]   # (Hkv, n)
+    rows = ((j // g) % c.tq)[None, :].expand(c.hkv, n)
+    gk = 2.0 * nd.q.float()[:, heads, rows]             # twice the query
+    gv = torch.full_like(gk, float("nan"))
+    return gk, gv
+
+
+def guarded(t: torch.Tensor, T: int, pre: int, post: int,
+            fill: torch.Tensor) -> torch.Tensor:
+    """A length-T view of `t`'s rows inside a larger buffer whose `pre` rows
+    before and `post` rows after hold `fill` (rotating). B = 1, Hkv = 1: the
+    size-1 dims hide the strides, so the view is is_contiguous() and passes
+    the bindings' checks without a copy."""
+    assert t.shape[0] == 1 and t.shape[1] == 1 and t.shape[2] == T
+    n = pre + T + post
+    buf = torch.empty(1, 1, n, t.shape[3], dtype=t.dtype, device=t.device)
+    f = fill.to(device=t.device)
+    nf = f.shape[2]
+    buf[:, :, :pre] = f[:, :, torch.arange(pre) % nf].to(t.dtype)
+    buf[:, :, pre + T:] = f[:, :, torch.arange(post) % nf].to(t.dtype)
+    buf[:, :, pre:pre + T] = t
+    view = buf[:, :, pre:pre + T]
+    assert view.is_contiguous() and view.data_ptr() != buf.data_ptr()
+    return view
+
+
+# --------------------------------------------------------------------------
+# fp64 oracle, mutable
+# --------------------------------------------------------------------------
+def _round_p(p: torch.Tensor, how: str) -> torch.Tensor:
+    if how == "e4m3":      # the fp8 kernels quantize 448 * P
+        return (p * 448.0).float().to(torch.float8_e4m3fn).double() / 448.0
+    return p.float().to(_TD[how]).double()
+
+
+def oracle(q, k, v, *, causal=False, q_offset=0, kv_offset=0, scale=None,
+           mutant=None, guard=None, p_round=None):
+    """Naive fp64 attention -> (out, lse), optionally MUTATED:
+
+    "mask+1" / "mask-1"    causal mask admits one key too many / hides the
+                           diagonal key
+    "kvoff+1" / "kvoff-1"  kv_offset off by one
+    "drop_last"            last key dropped (tail off-by-one)
+    "past_end"             one key past the end admitted (`guard` = the rows
+                           that lie there: (gk, gv))
+    ("vswap", a, b)        V rows a and b exchanged
+    "gqa_mod"              GQA head map h % Hkv instead of h // G
+    "row_transpose"        (head, row) order of the G*Tq row batch transposed
+    """
+    q, k, v = q.double(), k.double(), v.double()
+    b, hq, tq, d = q.shape
+    hkv = k.shape[1]
+    g = hq // hkv
+    scale = 1.0 / math.sqrt(d) if scale is None else scale
+    shift = 0
+    if mutant == "mask+1":
+        shift = 1
+    elif mutant == "mask-1":
+        shift = -1
+    elif mutant == "kvoff+1":
+        kv_offset += 1
+    elif mutant == "kvoff-1":
+        kv_offset -= 1
+    elif mutant == "drop_last":
+        k, v = k[:, :, :-1], v[:, :, :-1]
+    elif mutant == "past_end":
+        k = torch.cat([k, guard[0][:, :, :1].double()], 2)
+        v = torch.cat([v, guard[1][:, :, :1].double()], 2)
+    elif isinstance(mutant, tuple) and mutant[0] == "vswap":
+        v = v.clone()
+        v[:, :, [mutant[1], mutant[2]]] = v[:, :, [mutant[2], mutant[1]]]
+    elif mutant == "row_transpose":
+        q = q.reshape(b, hkv, tq, g, d).transpose(2, 3).reshape(b, hq, tq, d)
+    elif mutant not in (None, "gqa_mod"):
+        raise ValueError(mutant)
+    heads = torch.arange(hq)
+    kvh = heads % hkv if mutant == "gqa_mod" else heads // g
+    kk, vv = k[:, kvh], v[:, kvh]
+    tk = kk.shape[2]
+    if tk == 0:
+        return (torch.zeros(b, hq, tq, d, dtype=torch.float64),
+                torch.full((b, hq, tq), float("-inf"), dtype=torch.float64))
+    s = torch.matmul(q, kk.transpose(-1, -2)) * scale
+    if causal:
+        qpos = q_offset + torch.arange(tq)
+        kpos = kv_offset + torch.arange(tk)
+        s = s.masked_fill(kpos[None, :] > qpos[:, None] + shift,
+                          float("-inf"))
+    lse = torch.logsumexp(s, dim=-1)
+    m = s.amax(dim=-1, keepdim=True)
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    p = torch.exp(s - m)
+    den = p.sum(dim=-1, keepdim=True)
+    den = torch.where(den == 0, torch.ones_like(den), den)
+    if p_round:
+        p = _round_p(p, p_round)
+    return torch.matmul(p, vv) / den, lse
+
+
+def mutants(case: Case) -> list:
+    """Every mutant that applies to a case's family set. mask+1 / kvoff-1
+    need a hidden key to admit (first_masked); mask-1 / kvoff+1 need a
+    diagonal (diag); the length and V-placement mutants need the non-causal
+    seam family, where every key is visible."""
+    fam, out = case.families, []
+    if "first_masked" in fam:
+        out += ["mask+1", "kvoff-1"]
+    if "diag" in fam:
+        out += ["mask-1", "kvoff+1"]
+    if "seam" in fam:
+        out += ["drop_last", "past_end"]
+        if case.tkv > 1:
+            out.append(("vswap", 0, case.tkv - 1))
+        out += [("vswap", s - 1, s) for s in case.seams]
+    g = case.hq // case.hkv
+    if g > 1 and case.hkv > 1:
+        out.append("gqa_mod")
+    if g > 1 and case.tq > 1:
+        out.append("row_transpose")
+    return out
+
+
+def emulation_p_round(case: Case) -> str:
+    if case.kind in ("fp8", "mx_hw"):
+        return "e4m3"
+    return "fp16" if case.dtype == "fp16" else "bf16"
+
+
+@lru_cache(maxsize=None)
+def reference(case: Case, family: str):
+    """The fp32 oracle (ops/reference.flash_res_lse) every test compares
+    with; computed once per (case, family) and shared."""
+    from tree_attention_torch_amd.ops.reference import flash_res_lse
+
+    nd = build(case, family)
+    return flash_res_lse(nd.ref_q, nd.ref_k, nd.ref_v, nd.scale, nd.causal,
+                         nd.q_offset, nd.kv_offset)
+
+
+# --------------------------------------------------------------------------
+# the one comparison
+# --------------------------------------------------------------------------
+def compare(out, lse, ref_out, ref_lse, kind: str) -> None:
+    """assert_close at the project's bars for `kind`. `lse=None` compares
+    `out` alone (graph replay hands back no lse)."""
+    ob, lb = BARS[kind]
+    torch.testing.assert_close(out.detach().float().cpu(),
+                               ref_out.detach().float().cpu(),
+                               rtol=ob, atol=ob)
+    if lse is not None:
+        torch.testing.assert_close(lse.detach().float().cpu(),
+                                   ref_lse.detach().float().cpu(),
+                                   rtol=lb, atol=lb)
+
+
+def rejected(out, lse, ref_out, ref_lse, kind: str) -> bool:
+    try:
+        compare(out, lse, ref_out, ref_lse, kind)
+    except AssertionError:
+        return True
+    return False
+
+
+def check(nd: Needle, out, lse, what: str = "") -> None:
+    """compare() against the shared reference; on failure name the worst
+    row's target, the seam it sits at and the family."""
+    ref_out, ref_lse = reference(nd.case, nd.family)
+    try:
+        compare(out, lse, ref_out, ref_lse, nd.case.kind)
+    except AssertionError as e:
+        o = out.detach().float().cpu()
+        err = (o - ref_out).abs().nan_to_num(nan=float("inf")).amax(-1)[0]
+        h, r = divmod(int(err.argmax()), err.shape[1])
+        tgt = int(nd.targets[h, r])
+        near = min(nd.case.seams or (0,), key=lambda s: abs(s - tgt))
+        raise AssertionError(
+            f"{nd.case.id} [{nd.family}] {what}: worst row head {h} row {r} "
+            f"(position {nd.q_offset + r}) target key {tgt}, nearest seam "
+            f"{near}, seams {nd.case.seams}, cuts {nd.case.cuts}\n{e}"
+        ) from None
+
+
+# --------------------------------------------------------------------------
+# GPU runners (also used by the env-variant child processes)
+# --------------------------------------------------------------------------
+def _kv_dev(nd: Needle, use_guard: bool):
+    k, v = nd.k.cuda(), nd.v.cuda()
+    if use_guard:
+        gk, gv = guard_rows(nd, GUARD_PRE + GUARD_POST)
+        k = guarded(k, nd.case.tkv, GUARD_PRE, GUARD_POST, gk)
+        v = guarded(v, nd.case.tkv, GUARD_PRE, GUARD_POST, gv)
+    return k, v
+
+
+def run_kernel(nd: Needle, use_guard: bool = False):
+    """One (case, family) through the real entry point of its route."""
+    from tree_attention_torch_amd.ops import flash
+
+    ext = flash._load_extension()
+    assert ext is not None, "HIP extension must be built in-tree"
+    c, q = nd.case, nd.q.cuda()
+    args = (nd.scale, nd.causal, nd.q_offset, nd.kv_offset)
+    if c.route in ("mx_hw", "mx_dequant"):
+        return flash.local_attention_mx(q, *(t.cuda() for t in nd.mx), *args)
+    if c.route == "prefill_mx":
+        return ext.flash_attention_fp8_mx(q, *(t.cuda() for t in nd.mx),
+                                          *args)
+    k, v = _kv_dev(nd, use_guard)
+    if c.route in PREFILL_ROUTES:
+        assert c.tq > 16 // (c.hq // c.hkv)     # the binding's prefill side
+        return ext.flash_attention(q, k, v, *args)
+    if c.route == "spec":
+        assert flash.decode_loop_chunks(c.tq, c.hq // c.hkv, 1, c.hq) > 1
+    else:
+        assert c.route.startswith("decode"), c.route
+        assert c.tq * (c.hq // c.hkv) <= 16
+    return flash.local_attention(q, k, v, *args)
+
+
+def cache_buffers(nd: Needle, cap: int = CACHE_CAP):
+    """(1, Hkv, cap, D) K/V caches: the needle's keys as the live prefix,
+    the guard pattern (decoy K, NaN V) in every row at and past it."""
+    c = nd.case
+    gk, gv = guard_rows(nd, cap)
+    kc, vc = gk.to(nd.k.dtype).cuda(), gv.to(nd.v.dtype).cuda()
+    kc[:, :, :c.tkv] = nd.k.cuda()
+    vc[:, :, :c.tkv] = nd.v.cuda()
+    return kc, vc
+
+
+def run_cache(nd: Needle):
+    from tree_attention_torch_amd.ops import flash
+
+    ext = flash._load_extension()
+    kc, vc = cache_buffers(nd)
+    len_dev = torch.full((1,), nd.case.tkv, dtype=torch.long, device="cuda")
+    return ext.flash_attention_cache(nd.q.cuda(), kc, vc, len_dev, nd.scale)
+
+
+def run_sharded(nd: Needle):
+    """Per-shard partials with the global q_offset and the shard's
+    kv_offset, merged by combine_partials; plus the unsharded call."""
+    from tree_attention_torch_amd.ops import flash
+    from tree_attention_torch_amd.parallel.combine import combine_partials
+
+    c, q = nd.case, nd.q.cuda()
+    outs, lses = [], []
+    for lo, hi in zip(c.cuts[:-1], c.cuts[1:]):
+        if c.dtype == "mx":
+            k8, ks, v8, vs = (t.cuda() for t in nd.mx)
+            o, l = flash.local_attention_mx(
+                q, k8[:, :, lo:hi], ks[:, :, lo:hi], v8[:, :, lo:hi],
+                vs[:, :, lo // 32:hi // 32], nd.scale, nd.causal,
+                nd.q_offset, lo)
+        else:
+            o, l = flash.local_attention(
+                q, nd.k.cuda()[:, :, lo:hi], nd.v.cuda()[:, :, lo:hi],
+                nd.scale, nd.causal, nd.q_offset, lo)
+        outs.append(o)
+        lses.append(l)
+    merged = combine_partials(torch.stack(outs), torch.stack(lses))
+    if c.dtype == "mx":
+        whole = flash.local_attention_mx(q, *(t.cuda() for t in nd.mx),
+                                         nd.scale, nd.causal, nd.q_offset, 0)
+    else:
+        whole = flash.local_attention(q, nd.k.cuda(), nd.v.cuda(), nd.scale,
+                                      nd.causal, nd.q_offset, 0)
+    return merged, whole
+
+
+def variant_cases() -> list[Case]:
+    """The prefill rows the env-latched bf16 variants run."""
+    return [c for c in CASES if c.route == "prefill" and c.dtype == "bf16"]
+
+
+def run_variant_rows() -> None:
+    """Child-process body of the env-latched variant test: every bf16
+    prefill row of the table, every family, plain and guarded."""
+    n = 0
+    for c in variant_cases():
+        for fam in c.families:
+            nd = build(c, fam)
+            for use_guard in ((False, True) if c.guard else (False,)):
+                out, lse = run_kernel(nd, use_guard)
+                check(nd, out, lse, "guarded" if use_guard else "plain")
+                n += 1
+    torch.cuda.synchronize()
+    print(f"NEEDLES_OK {n}")

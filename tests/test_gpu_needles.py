@@ -1,0 +1,166 @@
+"""GPU (MI355X) needle tests: the shared case table of tests/needle_cases.py
+through the real entry points, compared with the fp32 oracle by the same
+`compare` (and bars) that tests/test_needle_sensitivity.py proves sensitive
+on the CPU: every row of the table rejects a causal mask off by one, a
+dropped or admitted tail key, V rows exchanged across each seam it names, a
+wrong GQA head map and a transposed (head, row) batch.
+
+Each query row is gain * K[target], so `out` names the key that was read.
+A failure prints the worst row's target key, the nearest seam and the family
+(docs/NEEDLE_TESTS.md lists which seams each kernel has).
+
+Guard rows (decoy K, NaN V) are ordinary allocated memory and NaN is data:
+nothing here reads or writes out of bounds on purpose.
+"""
+
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import needle_cases as nc
+
+pytestmark = pytest.mark.gpu
+
+KERNEL_ROUTES = ("decode", "decode_fp8", "decode_d64", "decode_narrow",
+                 "mx_hw", "spec") + nc.PREFILL_ROUTES
+
+
+def _params(routes):
+    out = []
+    for c in nc.CASES:
+        if c.route not in routes:
+            continue
+        for fam in c.families:
+            out.append(pytest.param(c, fam, False, id=f"{c.id}-{fam}"))
+            if c.guard:
+                out.append(pytest.param(c, fam, True,
+                                        id=f"{c.id}-{fam}-guarded"))
+    return out
+
+
+@pytest.fixture(scope="module")
+def ext():
+    from tree_attention_torch_amd.ops import flash
+
+    assert flash.hip_available(), "HIP extension must be built in-tree"
+    return flash._load_extension()
+
+
+@pytest.mark.parametrize("case,family,use_guard", _params(KERNEL_ROUTES))
+def test_needle_kernel(ext, monkeypatch, case, family, use_guard):
+    monkeypatch.delenv("TREE_ATTN_MX_DECODE", raising=False)
+    nd = nc.build(case, family)
+    out, lse = nc.run_kernel(nd, use_guard)
+    assert torch.isfinite(out).all(), f"{case.id} [{family}]: non-finite out"
+    nc.check(nd, out, lse, "guarded" if use_guard else "plain")
+
+
+@pytest.mark.parametrize("case,family,use_guard", _params(("mx_dequant",)))
+def test_needle_mx_dequant(ext, monkeypatch, case, family, use_guard):
+    """TREE_ATTN_MX_DECODE=dequant: the bf16-compute MX decode variant (the
+    binding reads the flag on every call)."""
+    monkeypatch.setenv("TREE_ATTN_MX_DECODE", "dequant")
+    nd = nc.build(case, family)
+    out, lse = nc.run_kernel(nd)
+    assert torch.isfinite(out).all()
+    nc.check(nd, out, lse, "dequant")
+
+
+_CACHE = [c for c in nc.CASES if c.route == "cache"]
+
+
+@pytest.mark.parametrize("case", _CACHE, ids=[c.id for c in _CACHE])
+def test_needle_cache(ext, case):
+    """ext.flash_attention_cache: live length from device memory over a
+    cap-1024 cache whose every row at and past the live length holds the
+    guard pattern. One row read past the live length is a NaN (or a decoy
+    that outscores the needle 4x), not 1/T of extra weight."""
+    nd = nc.build(case, "seam")
+    out, lse = nc.run_cache(nd)
+    assert torch.isfinite(out).all() and torch.isfinite(lse).all(), \
+        f"{case.id}: guard rows past live length {case.tkv} leaked"
+    nc.check(nd, out, lse, f"cache live={case.tkv}")
+
+
+def test_needle_cache_graph_replay(ext):
+    """DecodeSession.graphed_attend: capture once, replay at live lengths
+    511, 512, 513 (around the 512-key split seam) with the guard pattern
+    kept behind the live length."""
+    from tree_attention_torch_amd.session import DecodeSession
+
+    cases = [next(c for c in _CACHE if c.dtype == "bf16" and c.tkv == n)
+             for n in (511, 512, 513)]
+    sess = DecodeSession(1, 2, 128, max_tokens=768, device="cuda",
+                         kv_dtype="bf16", block=256)
+    assert sess.k.shape[2] == nc.CACHE_CAP
+
+    def load(nd):
+        kc, vc = nc.cache_buffers(nd)
+        sess.k.copy_(kc)
+        sess.v.copy_(vc)
+        sess.local_len = sess.total = nd.case.tkv
+        sess.sync_len()
+
+    nd0 = nc.build(cases[0], "seam")
+    load(nd0)
+    q_static = nd0.q.cuda().clone()
+    replay, _ = sess.graphed_attend(q_static)
+    for c in cases:
+        nd = nc.build(c, "seam")
+        load(nd)
+        q_static.copy_(nd.q.cuda())
+        out = replay()
+        torch.cuda.synchronize()
+        assert torch.isfinite(out).all(), f"replay at {c.tkv}: guard leaked"
+        nc.check(nd, out, None, f"graph replay live={c.tkv}")
+
+
+@pytest.mark.parametrize("flag,val", [
+    ("TREE_ATTN_PREFILL4", "1"), ("TREE_ATTN_PREFILL5", "1"),
+    ("TREE_ATTN_PREFILL6", "1"), ("TREE_ATTN_PREFILL6", "2"),
+    ("TREE_ATTN_PREFILL6", "7"), ("TREE_ATTN_PREFILL6", "0"),
+    ("TREE_ATTN_PREFILL_V1", "1"),
+])
+def test_needle_prefill_env_variants(ext, flag, val):
+    """The env-latched bf16 prefill kernels on the prefill rows of the table
+    (every family, plain and guarded). The route flag is latched at first
+    call, so each flag gets a fresh child process with its own timeout.
+    TREE_ATTN_PREFILL6=0 is the fallback fa_prefill2_kernel and
+    TREE_ATTN_PREFILL_V1 the first prefill kernel."""
+    tests_dir = os.path.dirname(os.path.abspath(__file__))
+    repo = os.path.dirname(tests_dir)
+    code = (f"import sys; sys.path.insert(0, {tests_dir!r}); "
+            "import needle_cases; needle_cases.run_variant_rows()")
+    env = {k: v for k, v in os.environ.items()
+           if not k.startswith("TREE_ATTN_PREFILL")}
+    env[flag] = val
+    env["PYTHONPATH"] = os.pathsep.join(
+        p for p in (repo, os.environ.get("PYTHONPATH")) if p)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True,
+                       text=True, env=env, timeout=300)
+    assert r.returncode == 0 and "NEEDLES_OK" in r.stdout, \
+        f"{flag}={val}: exit {r.returncode}\n{r.stdout[-3000:]}\n" \
+        f"{r.stderr[-3000:]}"
+
+
+_SHARDED = [pytest.param(c, f, id=f"{c.id}-{f}") for c in nc.CASES
+            if c.cuts for f in c.families]
+
+
+@pytest.mark.parametrize("case,family", _SHARDED)
+def test_needle_ranks_emulated(ext, monkeypatch, case, family):
+    """Ranks emulated on one GPU: the KV cut at uneven points that are no
+    tile multiples, local_attention(_mx) per shard with the global q_offset
+    and that shard's kv_offset, merged by combine_partials. One shard is
+    fully masked for some rows and partly masked for others. The merge must
+    equal the oracle AND the unsharded kernel call."""
+    monkeypatch.delenv("TREE_ATTN_MX_DECODE", raising=False)
+    nd = nc.build(case, family)
+    (out, lse), (w_out, w_lse) = nc.run_sharded(nd)
+    assert torch.isfinite(out).all()
+    nc.check(nd, out, lse, f"merged shards {case.cuts}")
+    nc.check(nd, w_out, w_lse, "unsharded")
+    nc.compare(out, lse, w_out, w_lse, case.kind)

@@ -49,7 +49,12 @@ def test_fp8_gqa_tree_attention_gpu():
     )
     out = ta.tree_attention(q, k, v)
     ref = ta.attention_reference(q.cpu(), k.cpu().float(), v.cpu().float())
-    torch.testing.assert_close(out.cpu(), ref, rtol=0.15, atol=0.15)
+    # This config is fp8 DECODE (q_len 1), so it takes the decode bar: worst
+    # max|dO| 0.0155 over the 25-case decode sweep (which holds this head
+    # layout at 8192 keys) x 2.5 = 4e-2, as in test_gpu_kernels.py
+    # _check_fp8_decode. On this exact config tools/fp8_err.py --tree
+    # measures 0.0029 (5 seeds, MI355X 2026-10-20).
+    torch.testing.assert_close(out.cpu(), ref, rtol=4e-2, atol=4e-2)
 
 
 def test_chunked_prefill_tree_attention_gpu():
