@@ -3,7 +3,10 @@ through the real entry points, compared with the fp32 oracle by the same
 `compare` (and bars) that tests/test_needle_sensitivity.py proves sensitive
 on the CPU: every row of the table rejects a causal mask off by one, a
 dropped or admitted tail key, V rows exchanged across each seam it names, a
-wrong GQA head map and a transposed (head, row) batch.
+wrong GQA head map and a transposed (head, row) batch; every row with B > 1
+a batch index dropped from a KV base, exchanged in an output offset or decoded
+transposed with the head; every row with a softmax scale of its own a kernel
+that ignores it.
 
 Each query row is gain * K[target], so `out` names the key that was read.
 A failure prints the worst row's target key, the nearest seam and the family
@@ -144,6 +147,103 @@ def test_needle_prefill_env_variants(ext, flag, val):
     assert r.returncode == 0 and "NEEDLES_OK" in r.stdout, \
         f"{flag}={val}: exit {r.returncode}\n{r.stdout[-3000:]}\n" \
         f"{r.stderr[-3000:]}"
+
+
+_REMAP = [pytest.param(c, f, id=f"{c.id}-{f}") for c in nc.remap_cases()
+          for f in c.families]
+
+
+@pytest.mark.parametrize("case,family", _REMAP)
+def test_needle_prefill_remap_off(ext, monkeypatch, case, family):
+    """TREE_ATTN_REMAP=0: fa_prefill7_kernel's plain block -> (batch, head,
+    q-block) decode on the rows that take the XCD remap by default (B*Hq in
+    {8, 24}) and on the B*Hq = 12 row. The launcher reads the flag on every
+    call."""
+    monkeypatch.setenv("TREE_ATTN_REMAP", "0")
+    nd = nc.build(case, family)
+    out, lse = nc.run_kernel(nd)
+    assert torch.isfinite(out).all(), f"{case.id} [{family}]: non-finite out"
+    nc.check(nd, out, lse, "TREE_ATTN_REMAP=0")
+
+
+_SESSION = [c for c in nc.CASES if c.route == "session"]
+_SESSIONS = {}
+
+
+def _filled_session(case):
+    """One DecodeSession per (kv dtype, length), shared by its rows and left
+    unchanged: the row's K/V stream through prefill() and seven append()s,
+    then what the session STORED of it, read back as fp32."""
+    from tree_attention_torch_amd.quant import (dequantize_k_mx,
+                                                dequantize_v_mx)
+    from tree_attention_torch_amd.session import DecodeSession
+
+    key = (case.dtype, case.tkv)
+    if key in _SESSIONS:
+        return _SESSIONS[key]
+    stream = nc.build(case, "seam")
+    k, v = stream.k.cuda(), stream.v.cuda()
+    sess = DecodeSession(case.b, case.hkv, case.d, max_tokens=768,
+                         device="cuda", kv_dtype=case.dtype, block=256)
+    n0 = case.tkv - 7
+    sess.prefill(k[:, :, :n0], v[:, :, :n0])
+    for t in range(n0, case.tkv):
+        sess.append(k[:, :, t:t + 1], v[:, :, t:t + 1])
+    assert sess.total == sess.local_len == case.tkv
+    if case.dtype == "mx":
+        n, tail = sess.q_len, sess.tail_len
+        assert (n, tail) == (case.tkv // 64 * 64, case.tkv % 64)
+        kf = torch.cat([
+            dequantize_k_mx(sess.k[:, :, :n].contiguous().cpu(),
+                            sess.ks[:, :, :n].contiguous().cpu()),
+            sess.k_tail[:, :, :tail].float().cpu()], 2)
+        vf = torch.cat([
+            dequantize_v_mx(sess.v[:, :, :n].contiguous().cpu(),
+                            sess.vs[:, :, :n // 32].contiguous().cpu()),
+            sess.v_tail[:, :, :tail].float().cpu()], 2)
+    else:
+        assert sess.k.shape[2] == nc.CACHE_CAP
+        kf = sess.k[:, :, :case.tkv].float().cpu()
+        vf = sess.v[:, :, :case.tkv].float().cpu()
+    # the stored KV is the stream in the cache's format (e4m3 keeps 3
+    # mantissa bits: half a step is 2^-4), batch by batch
+    tol = 0.0 if case.dtype == "bf16" else 0.07
+    torch.testing.assert_close(kf, stream.k.float(), rtol=tol, atol=tol)
+    torch.testing.assert_close(vf, stream.v.float(), rtol=tol, atol=tol)
+    _SESSIONS[key] = (sess, kf, vf)
+    return _SESSIONS[key]
+
+
+@pytest.mark.parametrize("case", _SESSION, ids=[c.id for c in _SESSION])
+def test_needle_session(ext, monkeypatch, case):
+    """DecodeSession(2, 2, 128) at world size 1, kv_dtype bf16 / fp8 / mx,
+    576 tokens (MX: nine quantized windows) and 600 (MX: plus a 24-token
+    bf16 staging tail): q = gain * K_stored[target], attend(q) and
+    attend(q, softmax_scale=0.05) against flash_res_lse over the KV the
+    session stored. attend() hands back no lse, so the local partial's lse
+    (the only output that shows a scale that was ignored) is compared too."""
+    from tree_attention_torch_amd.ops.reference import flash_res_lse
+    from tree_attention_torch_amd.parallel.combine import combine_partials
+
+    monkeypatch.delenv("TREE_ATTN_MX_DECODE", raising=False)
+    sess, kf, vf = _filled_session(case)
+    nd = nc.build_from(case, "seam", None, None, None, kf, vf)
+    n = sess.q_len if case.dtype == "mx" else case.tkv
+    ref = flash_res_lse(nd.ref_q, kf[:, :, :n], vf[:, :, :n], nd.scale)
+    if n < case.tkv:
+        # the MX kernel rounds Q to e4m3 (nd.ref_q); the bf16 kernel of the
+        # staging tail reads the query as it is
+        tail = flash_res_lse(nd.q.float(), kf[:, :, n:], vf[:, :, n:],
+                             nd.scale)
+        ref = combine_partials(torch.stack([ref[0], tail[0]]),
+                               torch.stack([ref[1], tail[1]]))
+    q = nd.q.cuda()
+    scale_arg = (case.scale,) if case.scale else ()
+    out = sess.attend(q, *scale_arg)
+    assert torch.isfinite(out).all(), f"{case.id}: non-finite out"
+    nc.check(nd, out, None, "attend", ref=ref)
+    out_l, lse_l = sess._local_partial(q, *(scale_arg or (None,)))
+    nc.check(nd, out_l, lse_l, "local partial", ref=ref)
 
 
 _SHARDED = [pytest.param(c, f, id=f"{c.id}-{f}") for c in nc.CASES

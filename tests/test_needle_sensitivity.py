@@ -10,8 +10,8 @@ For every row of the shared table:
 * every applicable mutant is REJECTED on at least one family of the row's
   set - a condition, not a measurement: a row that lets one through fails,
 * an oracle that emulates the kernel's arithmetic (inputs in the storage
-  dtype, P rounded to bf16/fp16/e4m3 before PV, Q rounded to e4m3 for MX)
-  stays INSIDE `compare`, so the bars are reachable.
+  dtype, P rounded to bf16/fp16/e4m3 before PV, Q rounded to e4m3 for fp8
+  and MX) stays INSIDE `compare`, so the bars are reachable.
 """
 
 import pytest
@@ -33,7 +33,7 @@ def test_table_covers_the_routes():
     assert routes == {"decode", "decode_fp8", "decode_d64", "decode_narrow",
                       "mx_hw", "mx_dequant", "spec", "cache",
                       "prefill", "prefill_d64", "prefill_fp8", "prefill_mx",
-                      "sharded", "sharded_mx"}
+                      "sharded", "sharded_mx", "session"}
     assert all(c.tkv <= 1024 for c in nc.CASES)
     assert nc.variant_cases(), "the env-variant children need prefill rows"
     # the emulated-rank prefill rows must reach the prefill kernels through
@@ -42,10 +42,27 @@ def test_table_covers_the_routes():
                                                     mx_decode_shaped)
     for c in nc.CASES:
         if c.cuts and c.tq > 16:
-            assert decode_loop_chunks(c.tq, c.hq // c.hkv, 1, c.hq) == 0
+            assert decode_loop_chunks(c.tq, c.hq // c.hkv, c.b, c.hq) == 0
             assert not mx_decode_shaped(c.hq, c.hkv, c.tq)
         if c.route == "spec":
-            assert decode_loop_chunks(c.tq, c.hq // c.hkv, 1, c.hq) > 1
+            assert decode_loop_chunks(c.tq, c.hq // c.hkv, c.b, c.hq) > 1
+        # only B = 1, Hkv = 1 hides the strides of a guarded view
+        assert not c.guard or (c.b == 1 and c.hkv == 1)
+    assert any(c.route == "spec" and c.b > 1 for c in nc.CASES)
+    # every route runs with B > 1 and with a softmax scale of its own
+    for route in routes:
+        assert any(c.route == route and c.b > 1 for c in nc.CASES), route
+        if not route.startswith("sharded"):
+            assert any(c.route == route and c.scale for c in nc.CASES), route
+    # the gen7/gen9 remap: B*Hq % 8 == 0 with b = 0 only, with one 8-group
+    # holding both batches, with an 8-group that straddles two batches
+    # (Hq % 8 != 0), and the other branch with B > 1
+    for dt in ("bf16", "fp16"):
+        bh = {(c.b, c.hq) for c in nc.CASES
+              if c.route == "prefill" and c.dtype == dt}
+        assert {(1, 8), (2, 4), (2, 12), (3, 4)} <= bh
+    assert {(c.b, c.hq) for c in nc.remap_cases()} >= \
+        {(1, 8), (2, 4), (2, 12), (3, 4)}
 
 
 @pytest.mark.parametrize("case", nc.CASES, ids=CASE_IDS)
@@ -57,11 +74,11 @@ def test_needles_are_one_hot(case):
     for fam in (f for f in case.families if f != "first_masked"):
         nd = nc.build(case, fam)
         out, lse = nc.reference(case, fam)
-        g = case.hq // case.hkv
-        kvh = torch.arange(case.hq) // g
-        want = nd.ref_v[:, kvh[:, None], nd.targets]
-        tscore = (nd.ref_q * nd.ref_k[:, kvh[:, None], nd.targets]).sum(-1) \
-            * nd.scale
+        assert nd.targets.shape == (case.b, case.hq, case.tq)
+        assert nd.scale == case.softmax_scale
+        want = nc.take_rows(nd.ref_v, case, nd.targets)
+        tscore = (nd.ref_q * nc.take_rows(nd.ref_k, case, nd.targets)
+                  ).sum(-1) * nd.scale
         # D=32 needles score 11.3 against ~1000 keys of N(0, 2): still > 90 %
         tol = 0.05 if case.d >= 64 else 0.6
         assert (out - want).abs().max() < tol, (case.id, fam)
@@ -102,8 +119,13 @@ def test_every_mutant_is_rejected(case):
 def test_emulated_kernel_is_inside_the_bars(case):
     for fam in case.families:
         nd = nc.build(case, fam)
-        out, lse = _oracle(nd, p_round=nc.emulation_p_round(case))
+        out, lse = _oracle(nd, p_round=nc.emulation_p_round(case),
+                           q_round=nc.emulation_q_round(case))
         nc.compare(out, lse, *nc.reference(case, fam), case.kind)
+        if case.kind == "fp8":
+            # the fp8 kernels cast Q to e4m3: every query is exact there,
+            # so the reference (which reads nd.q) sees what the kernel sees
+            assert torch.equal(nc._e4m3(nd.q), nd.q.float()), (case.id, fam)
 
 
 @pytest.mark.parametrize(
