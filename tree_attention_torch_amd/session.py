@@ -29,7 +29,7 @@ import torch.distributed as dist
 from .ops.flash import local_attention
 from .parallel.combine import combine_partials, tree_combine
 
-__all__ = ["DecodeSession"]
+__all__ = ["DecodeSession", "RaggedDecodeSession"]
 
 _DTYPES = {
     "bf16": torch.bfloat16,
@@ -363,3 +363,341 @@ class DecodeSession:
                 self.local_len += n
             self.total += n
             t += n
+
+
+# --------------------------------------------------------------------------
+# ragged batch: one length per sequence
+# --------------------------------------------------------------------------
+def _place(t: int, block: int, world: int) -> tuple[int, int]:
+    """(owning rank, local position) of global token t: the block-cyclic
+    formula of the module docstring. kv_append_kernel (ops/hip) computes the
+    same two numbers on the device."""
+    blk = t // block
+    return blk % world, block * (blk // world) + t % block
+
+
+def _empty_partial(q: torch.Tensor):
+    """The partial of a shard that holds no key: out = 0, lse = -inf."""
+    b, hq, tq, d = q.shape
+    out_l = torch.zeros(b, hq, tq, d, dtype=torch.float32, device=q.device)
+    lse_l = torch.full((b, hq, tq), float("-inf"), dtype=torch.float32,
+                       device=q.device)
+    return out_l, lse_l
+
+
+def _zero_copy_ok(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """The predicate of DecodeSession._local_partial (it mirrors the
+    TORCH_CHECKs of bindings.cpp flash_attention_cache): D=128; q bf16/fp16;
+    cache dtype == q dtype or fp8 cache under a bf16 q; (Hq/Hkv)*Tq <= 16."""
+    return (
+        q.device.type == "cuda"
+        and k.size(3) == 128
+        and q.dtype in (torch.bfloat16, torch.float16)
+        and (
+            k.dtype == q.dtype
+            or (k.dtype == torch.float8_e4m3fn and q.dtype == torch.bfloat16)
+        )
+        and (q.shape[1] // k.shape[1]) * q.shape[2] <= 16
+    )
+
+
+class RaggedDecodeSession:
+    """Token-by-token decode of a BATCH whose sequences have their own
+    lengths, over the same block-cyclic sharded cache as DecodeSession.
+
+    Sequences join (prefill), grow (append with an ``active`` mask) and
+    leave (reset) independently. The lengths live twice: ``total_dev`` /
+    ``local_len_dev`` (B,) int64 on the device are what the kernels read, so
+    a whole step (append kernel, cache kernel, split combine) replays from
+    one hipGraph; ``totals`` / ``local_lens`` are the host mirror, advanced
+    by the same formula. The host decides which rows are active, so the
+    mirror is always exact, and capacity is checked on it before any launch.
+
+    ``max_tokens`` is per sequence. Tq = 1; no MX cache (its 64-token
+    quantization windows are host-side state per sequence).
+    """
+
+    def __init__(
+        self,
+        batch: int,
+        kv_heads: int,
+        head_dim: int,
+        max_tokens: int,
+        device: torch.device | str = "cuda",
+        kv_dtype: str | torch.dtype = "bf16",
+        block: int = 256,
+        group: dist.ProcessGroup | None = None,
+    ) -> None:
+        if isinstance(kv_dtype, str) and kv_dtype in ("mx", "fp8_mx"):
+            raise ValueError(
+                "RaggedDecodeSession: the MX cache keeps host-side window "
+                "state per sequence and is not supported; use bf16, fp16, "
+                "fp32 or fp8")
+        if isinstance(kv_dtype, str) and kv_dtype not in _DTYPES:
+            raise ValueError(f"RaggedDecodeSession: unknown kv_dtype "
+                             f"{kv_dtype!r}")
+        self.device = torch.device(device)
+        if dist.is_available() and dist.is_initialized():
+            self.rank = dist.get_rank(group)
+            self.world = dist.get_world_size(group)
+        else:
+            self.rank, self.world = 0, 1
+        self.group = group
+        self.block = block
+        self.batch = batch
+        blocks_total = (max_tokens + block - 1) // block + 1
+        local_cap = ((blocks_total + self.world - 1) // self.world) * block
+        td = _DTYPES[kv_dtype] if isinstance(kv_dtype, str) else kv_dtype
+        self.k = torch.empty(batch, kv_heads, local_cap, head_dim, dtype=td,
+                             device=self.device)
+        self.v = torch.empty_like(self.k)
+        self.total_dev = torch.zeros(batch, dtype=torch.long,
+                                     device=self.device)
+        self.local_len_dev = torch.zeros_like(self.total_dev)
+        self.totals = [0] * batch       # global tokens of each sequence
+        self.local_lens = [0] * batch   # of them, in THIS rank's shard
+        self._mask_cache: dict[tuple, torch.Tensor] = {}
+
+    # ---- host mirror ----
+    @property
+    def capacity(self) -> int:
+        return self.k.size(2)
+
+    @property
+    def _row_bytes(self) -> int:
+        return self.k.size(3) * self.k.element_size()
+
+    def _mask(self, active) -> list[bool]:
+        if active is None:
+            return [True] * self.batch
+        if isinstance(active, torch.Tensor):
+            active = active.tolist()
+        mask = [bool(a) for a in active]
+        if len(mask) != self.batch:
+            raise ValueError(f"active has {len(mask)} entries for a batch of "
+                             f"{self.batch}")
+        return mask
+
+    def _mask_dev(self, mask: list[bool]) -> torch.Tensor:
+        """The mask as a (B,) uint8 device tensor. Masks seen before come
+        from a small cache: a host-to-device copy from pageable memory makes
+        the host wait for the stream, once per step, which is what a
+        launch-bound decode step cannot afford."""
+        key = tuple(mask)
+        dev = self._mask_cache.get(key)
+        if dev is None:
+            if len(self._mask_cache) >= 256:
+                self._mask_cache.clear()
+            dev = torch.tensor(mask, dtype=torch.uint8).to(self.device)
+            self._mask_cache[key] = dev
+        return dev
+
+    def _check_capacity(self, mask: list[bool]) -> None:
+        """Raise before anything is launched or stored, naming the row."""
+        for b, on in enumerate(mask):
+            if not on:
+                continue
+            owner, pos = _place(self.totals[b], self.block, self.world)
+            if owner == self.rank and pos >= self.capacity:
+                raise RuntimeError(
+                    f"RaggedDecodeSession capacity exceeded: row {b} local "
+                    f"shard full at {self.local_lens[b]} tokens (grow "
+                    f"max_tokens)")
+
+    def _advance(self, mask: list[bool]) -> None:
+        for b, on in enumerate(mask):
+            if not on:
+                continue
+            owner, pos = _place(self.totals[b], self.block, self.world)
+            if owner == self.rank:
+                self.local_lens[b] = pos + 1
+            self.totals[b] += 1
+
+    def _push_lengths(self, b: int) -> None:
+        self.total_dev[b : b + 1].fill_(self.totals[b])
+        self.local_len_dev[b : b + 1].fill_(self.local_lens[b])
+
+    def _append_kernel_ok(self) -> bool:
+        return self.device.type == "cuda" and self._row_bytes % 4 == 0
+
+    @staticmethod
+    def _ext():
+        from .ops.flash import _load_extension
+
+        ext = _load_extension()
+        if ext is None:
+            raise RuntimeError(
+                "RaggedDecodeSession: the gfx950 HIP extension "
+                "_tree_attn_hip is not built but the session is on a GPU")
+        return ext
+
+    # ---- cache updates ----
+    def prefill(self, b: int, k_seq: torch.Tensor, v_seq: torch.Tensor) -> None:
+        """Bulk-load the prompt of sequence b, (Hkv, T, D) or (1, Hkv, T, D),
+        behind what it already holds; chunks split at that sequence's own
+        block boundaries (DecodeSession.prefill's ownership rule)."""
+        if k_seq.dim() == 4:
+            k_seq, v_seq = k_seq[0], v_seq[0]
+        t_total = k_seq.shape[1]
+        chunks = []   # (source offset, n, local position) of the owned ones
+        total, t = self.totals[b], 0
+        while t < t_total:
+            n = min(self.block - total % self.block, t_total - t)
+            owner, pos = _place(total, self.block, self.world)
+            if owner == self.rank:
+                if pos + n > self.capacity:
+                    raise RuntimeError(
+                        f"RaggedDecodeSession capacity exceeded during "
+                        f"prefill: row {b} at {pos}+{n} tokens (grow "
+                        f"max_tokens)")
+                chunks.append((t, n, pos))
+            total += n
+            t += n
+        for t, n, pos in chunks:
+            self.k[b, :, pos : pos + n] = k_seq[:, t : t + n].to(self.k.dtype)
+            self.v[b, :, pos : pos + n] = v_seq[:, t : t + n].to(self.v.dtype)
+            self.local_lens[b] = pos + n
+        self.totals[b] = total
+        self._push_lengths(b)
+
+    def append(self, k_new: torch.Tensor, v_new: torch.Tensor,
+               active=None) -> None:
+        """Append one token's K/V (B, Hkv, 1, D) to every ACTIVE sequence
+        (host bool sequence or CPU tensor of length B; None: all). Every
+        rank calls this with the same arguments; only a token's owning rank
+        stores it."""
+        mask = self._mask(active)
+        self._check_capacity(mask)
+        if self._append_kernel_ok():
+            # the cast to the cache dtype (fp8 included) stays a torch op;
+            # the kernel copies bytes
+            self._ext().kv_cache_append(
+                self.k, self.v, k_new.to(self.k.dtype).contiguous(),
+                v_new.to(self.v.dtype).contiguous(), self.total_dev,
+                self.local_len_dev, self._mask_dev(mask), self.block,
+                self.rank, self.world)
+            self._advance(mask)
+            return
+        for b, on in enumerate(mask):
+            if not on:
+                continue
+            owner, pos = _place(self.totals[b], self.block, self.world)
+            if owner == self.rank:
+                self.k[b, :, pos : pos + 1] = k_new[b].to(self.k.dtype)
+                self.v[b, :, pos : pos + 1] = v_new[b].to(self.v.dtype)
+        self._advance(mask)
+        self.total_dev.copy_(torch.tensor(self.totals, dtype=torch.long))
+        self.local_len_dev.copy_(torch.tensor(self.local_lens,
+                                              dtype=torch.long))
+
+    def reset(self, b: int) -> None:
+        """Free slot b for a new sequence: its lengths go to 0 on host and
+        device; nothing is cleared."""
+        self.totals[b] = 0
+        self.local_lens[b] = 0
+        self._push_lengths(b)
+
+    # ---- attention ----
+    def _local_partial(self, q: torch.Tensor, softmax_scale: float | None):
+        if _zero_copy_ok(q, self.k):
+            # one launch for the whole ragged batch: every block clips its
+            # chunk to its own row's length, read from local_len_dev
+            scale = (softmax_scale if softmax_scale is not None
+                     else 1.0 / math.sqrt(q.shape[-1]))
+            return self._ext().flash_attention_cache(
+                q.contiguous(), self.k, self.v, self.local_len_dev, scale)
+        outs, lses = [], []
+        for b, n in enumerate(self.local_lens):
+            qb = q[b : b + 1]
+            if n > 0:
+                o, l = local_attention(qb, self.k[b : b + 1, :, :n].contiguous(),
+                                       self.v[b : b + 1, :, :n].contiguous(),
+                                       softmax_scale)
+            else:
+                o, l = _empty_partial(qb)
+            outs.append(o)
+            lses.append(l)
+        return torch.cat(outs), torch.cat(lses)
+
+    def attend(self, q: torch.Tensor, softmax_scale: float | None = None,
+               combine: str = "auto") -> torch.Tensor:
+        """Attention of q (B, Hq, 1, D), row b over sequence b's cached
+        tokens -> (B, Hq, 1, D). A sequence that holds no token yields an
+        all-zero row."""
+        out_l, lse_l = self._local_partial(q, softmax_scale)
+        out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
+        return out
+
+    def graphed_step(self, q_static: torch.Tensor, k_static: torch.Tensor,
+                     v_static: torch.Tensor,
+                     softmax_scale: float | None = None,
+                     combine: str = "auto"):
+        """Capture one decode step — append kernel, cache kernel, split
+        combine, one linear chain — into a hipGraph. Returns ``replay``.
+
+        Write the step's query and new K/V (B, Hkv, 1, D) into the static
+        tensors, then ``replay(active=None)`` checks capacity on the host
+        mirror, advances it, copies the mask into the static device buffer
+        the capture reads, replays, and returns the output: the static
+        buffer at world size 1; at world size > 1 the local partial replays
+        from the graph and the collective runs eagerly (graphed_attend).
+        """
+        if self.device.type != "cuda":
+            raise ValueError("graphed_step needs a GPU session")
+        # never capture the slicing path: it would freeze the capture-time
+        # lengths into every replay
+        if not _zero_copy_ok(q_static, self.k):
+            raise ValueError(
+                "graphed_step: the zero-copy cache kernel does not take this "
+                "session (needs head_dim 128, a bf16/fp16 query, a cache of "
+                "the query's dtype or fp8 under bf16, and Hq/Hkv <= 16)")
+        if not self._append_kernel_ok():
+            raise ValueError("graphed_step: the append kernel needs cache "
+                             "rows of a multiple of 4 bytes")
+        ext = self._ext()
+        active_dev = torch.zeros(self.batch, dtype=torch.uint8,
+                                 device=self.device)
+        scale = (softmax_scale if softmax_scale is not None
+                 else 1.0 / math.sqrt(q_static.shape[-1]))
+
+        def step():
+            ext.kv_cache_append(
+                self.k, self.v, k_static.to(self.k.dtype).contiguous(),
+                v_static.to(self.v.dtype).contiguous(), self.total_dev,
+                self.local_len_dev, active_dev, self.block, self.rank,
+                self.world)
+            return ext.flash_attention_cache(
+                q_static.contiguous(), self.k, self.v, self.local_len_dev,
+                scale)
+
+        # warm-up on a side stream (allocator + kernels) under an all-zero
+        # mask, so no length moves; then capture
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                step()
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out_l, lse_l = step()
+        self._graph = graph  # keep alive
+        self._active_dev = active_dev
+
+        in_buffer = [[False] * self.batch]   # what active_dev holds now
+
+        def replay(active=None) -> torch.Tensor:
+            mask = self._mask(active)
+            self._check_capacity(mask)
+            self._advance(mask)
+            if mask != in_buffer[0]:   # a steady mask costs no copy at all
+                active_dev.copy_(self._mask_dev(mask))
+                in_buffer[0] = mask
+            graph.replay()
+            if self.world == 1:
+                return out_l
+            out, _ = tree_combine(out_l, lse_l, strategy=combine,
+                                  group=self.group)
+            return out
+
+        return replay
