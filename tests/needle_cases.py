@@ -10,10 +10,19 @@ moves the answer by O(1). Rows with B > 1 hold different K/V (and targets)
 in every batch; rows with a softmax scale of their own pick the gain from the
 scale (needle_gain), and a kernel that ignores the scale shows in ``lse``.
 
+The many-split rows (more than two splits of the split-KV decode kernels)
+put a needle in every split and on both sides of every split seam; their
+``pair`` family is ``gain * (K[t1] + K[t2])`` with the two targets in
+different splits at weights between 0.67 / 0.33 and 0.82 / 0.18, so that the
+combine has to weigh two live splits right.
+
 This module is a plain helper (not a conftest). It holds
 
 * the needle builders and the shared CASE TABLE,
+* ``split_plan``, the binding's split heuristic for any length,
 * an fp64 naive attention that can be MUTATED (the errors the suite must see),
+* an fp64 SPLIT oracle (partials by ``split_plan``, merged by the stable
+  algebra) and the split / combine mutants of it,
 * ``guarded``: K/V views with decoy-K / NaN-V rows on both sides,
 * ``compare``: the project's existing bars, used by BOTH the CPU sensitivity
   tests (tests/test_needle_sensitivity.py) and the GPU tests
@@ -80,6 +89,8 @@ class Case:
     note: str = ""
     b: int = 1             # batch; every batch holds different K/V
     scale: float = 0.0     # softmax scale; 0: 1/sqrt(d)
+    cap: int = 0           # cache rows: capacity; 0: CACHE_CAP
+    tile: int = 0          # many-split rows: keys per tile of the kernel
 
     @property
     def softmax_scale(self) -> float:
@@ -113,18 +124,70 @@ class Case:
             s += f"-b{self.b}"
         if self.scale:
             s += f"-s{self.scale:g}"
+        if self.cap:
+            s += f"-cap{self.cap}"
         return s
 
+    @property
+    def capacity(self) -> int:
+        return self.cap or CACHE_CAP
 
-def split_chunk(b: int, hkv: int, tkv: int) -> int:
-    """Keys per split of the split-KV decode kernels. Mirrors the binding's
-    split heuristic for tkv <= 1024 (at most two splits, chunk a multiple of
-    128); used only to NAME the split seam a case targets."""
-    max_s = -(-tkv // 512)
+    @property
+    def plan(self):
+        """(S, chunk) of the split-KV call this row makes (the cache kernel
+        plans over its capacity, a spec row per query chunk); None for the
+        routes that make no single split-KV call."""
+        if self.route == "cache":
+            return split_plan(self.b, self.hkv, self.capacity)
+        if self.route.startswith("decode") or self.route in (
+                "mx_hw", "mx_dequant", "spec"):
+            return split_plan(self.b, self.hkv, self.tkv)
+        return None
+
+    @property
+    def live_splits(self) -> int:
+        """Splits that hold at least one live key."""
+        return -(-self.tkv // self.plan[1])
+
+    @property
+    def combine_groups(self) -> int:
+        """NG of fa_combine_kernel: 512 / partial width (narrow heads are
+        padded to 128)."""
+        return 8 if self.d == 64 else 4
+
+
+SPLIT_TARGET = 512   # the binding's grid target with the env knob unset
+
+
+def split_plan(b: int, hkv: int, tkv: int) -> tuple:
+    """(S, chunk) of the split-KV decode kernels over tkv keys: pick_splits
+    and plan_splits of ops/hip/bindings.cpp in full, for any length, with
+    TREE_ATTN_SPLIT_BLOCKS unset (the GPU tests assert that). Chunks are no
+    shorter than clamp(tkv / 64, 512, 2048) keys; the grid target is 512
+    blocks when B*Hkv divides it and 768 otherwise; the chunk is rounded up
+    to 128 keys and S recomputed from it (40000 keys: 64 -> 63 splits of
+    640). Used to NAME the split seams a case targets and to cut the split
+    oracle; pinned by a table in tests/test_needle_sensitivity.py."""
+    min_chunk = min(max(tkv // 64, 512), 2048)
+    max_s = -(-tkv // min_chunk)
     bh = b * hkv
-    s = 512 // bh if 512 % bh == 0 else -(-768 // bh)
+    if bh <= SPLIT_TARGET and SPLIT_TARGET % bh == 0:
+        s = SPLIT_TARGET // bh
+    else:
+        s = (SPLIT_TARGET * 3 // 2 + bh - 1) // bh
     s = max(1, min(s, max_s))
-    return (-(-tkv // s) + 127) // 128 * 128
+    chunk = (-(-tkv // s) + 127) // 128 * 128
+    return -(-tkv // chunk), chunk
+
+
+def assert_default_split_plan() -> None:
+    """split_plan mirrors the binding only while its grid target is the
+    default; a GPU test that relies on the seams says so loudly."""
+    import os
+
+    assert "TREE_ATTN_SPLIT_BLOCKS" not in os.environ, \
+        "TREE_ATTN_SPLIT_BLOCKS is set: needle_cases.split_plan (and every " \
+        "split seam the case table names) mirrors the default grid target"
 
 
 def pick_seams(tkv: int, tile: int, rows: int, chunk: int = 0,
@@ -163,7 +226,7 @@ def seam_targets(case: Case) -> list[int]:
         if 0 <= c < t and c not in seen:
             seen.add(c)
             out.append(c)
-    assert len(out) <= case.hq * case.tq, \
+    assert len(out) <= case.b * case.hq * case.tq, \
         f"{case.id}: {len(out)} seam targets do not fit the query rows"
     return out
 
@@ -179,16 +242,24 @@ def _build_table() -> list[Case]:
 
     def add(route, dtype, hq, hkv, tkv, tq, tile, *, d=128, sub=0, guard=False,
             chunk=True, families=None, q_offset=-1, cuts=(), note="", b=1,
-            scale=0.0):
-        ch = split_chunk(b, hkv, tkv) if chunk else 0
-        seams = pick_seams(tkv, tile, hq * tq, ch, sub)
+            scale=0.0, many=False, seams=None):
+        # a many-split row sizes its seam set by ALL its rows (B*Hq*Tq: the
+        # rotation of family_targets runs on over the batches) and adds the
+        # `pair` family; every other row keeps the seams it always had
+        ch = split_plan(b, hkv, tkv)[1] if chunk else 0
+        rows = (b if many else 1) * hq * tq
+        if seams is None:
+            seams = pick_seams(tkv, tile, rows, ch, sub)
         if cuts:
             seams = tuple(dict.fromkeys(tuple(cuts[1:-1]) + seams))[
-                : (hq * tq - 2) // 2]
+                : (rows - 2) // 2]
         fam = families or _decode_family(tkv, tq)
+        if many and route != "spec" and not cuts:
+            fam = fam + ("pair",)
         cases.append(Case(route, dtype, hq, hkv, tkv, tq, fam, seams, d,
                           q_offset, guard and hkv == 1 and b == 1,
-                          tuple(cuts), note, b, scale))
+                          tuple(cuts), note, b, scale, 0,
+                          tile if many else 0))
 
     # -- bf16/fp16 split-KV decode (fa_fwd_kernel): 64-key tiles, chunk a
     #    multiple of 128, second split above 512 keys (513 -> 384 + 129)
@@ -370,12 +441,89 @@ def _build_table() -> list[Case]:
         for tkv in (576, 600):
             if dt == "mx":
                 seams = ((576,) if tkv > 576 else ()) + \
-                    pick_seams(576, tile, 30, split_chunk(2, 2, 576))
+                    pick_seams(576, tile, 30, split_plan(2, 2, 576)[1])
             else:
                 seams = pick_seams(tkv, tile, 32, 512)
             for sc in (0.0, 0.05):
                 cases.append(Case("session", dt, 8, 2, tkv, 4, ("seam",),
                                   seams, b=2, scale=sc))
+    # ---------------------------------------------------------------------
+    # many splits (S > 2): needles in every split, both sides of every split
+    # seam, and the `pair` family (two live splits weighted by the combine).
+    # fa_combine_kernel reduces `for (s = g; s < S; s += NG)` with NG = 4 at
+    # width 128 (narrow heads are padded to it) and 8 at D = 64: S = NG + 1
+    # and 2 NG + 1 make that loop take a second and a third step. Each row
+    # is the shortest length that reaches its (S, chunk); split seams come
+    # first in pick_seams, tile seams fill what rows are left.
+    # ---------------------------------------------------------------------
+    def frontier(route, dtype, tile, tkv, qo, note):
+        # G = 2, Tq = 8 causal; B = 2 gives the 32 rows nine splits need
+        add(route, dtype, 2, 1, tkv, 8, tile, q_offset=qo, b=2, many=True,
+            note=note)
+
+    def many_40000(route, dtype, tile):
+        # 63 splits of 640 keys, 64 rows (at most 16 rows G*Tq fit per KV
+        # head): both sides of the 31 odd seams plus keys 0 and 39999
+        add(route, dtype, 32, 2, 40000, 1, tile, b=2, many=True,
+            seams=tuple(range(640, 40000, 1280)),
+            note="64 rows: every one of the 63 splits holds a target, both "
+                 "sides of the 31 odd split seams are targets, the even "
+                 "seams have no row left")
+
+    add("decode", "bf16", 8, 2, 1100, 4, 64, many=True)    # S=3, chunk 384
+    add("decode", "bf16", 8, 2, 2049, 4, 64, many=True)    # S=5, 1-key tail
+    add("decode", "bf16", 8, 2, 2560, 4, 64, many=True)    # S=5, full
+    add("decode", "bf16", 8, 2, 4097, 4, 64, many=True)    # S=9 = 2 NG + 1
+    # (2554: at 2555..2559 the draw leaves one diag row 0.051 off its
+    # target's V row, past the 0.05 the one-hot condition asks)
+    frontier("decode", "bf16", 64, 4097, 2554,
+             "frontier 2554..2561 inside split 5: splits 6..8 all-masked "
+             "for every row, split 5 for rows 0..5")
+    add("decode", "bf16", 3, 3, 2049, 4, 64, b=3, many=True)  # bh = 9
+    add("decode", "fp16", 8, 2, 2049, 4, 64, many=True)
+    many_40000("decode", "bf16", 64)
+    add("decode_fp8", "fp8", 8, 2, 2049, 4, 128, many=True)
+    add("decode_fp8", "fp8", 8, 2, 4097, 4, 128, many=True)
+    frontier("decode_fp8", "fp8", 128, 4097, 2554, "as the bf16 row")
+    many_40000("decode_fp8", "fp8", 128)
+    add("decode_d64", "bf16", 8, 2, 4097, 4, 128, d=64, many=True)  # NG + 1
+    add("decode_d64", "bf16", 8, 2, 8193, 4, 128, d=64, b=2, many=True,
+        note="S = 17 = 2 NG + 1: 64 rows for 33 split targets")
+    add("decode_d64", "fp16", 8, 2, 4097, 4, 128, d=64, many=True)
+    for d in (80, 96, 112):
+        for tkv in (2049, 4097):
+            add("decode_narrow", "bf16", 8, 2, tkv, 4, 128, d=d, many=True)
+    # every narrow instantiation has a needle row (D = 32 / 48 needles are
+    # not sharp enough at thousands of keys: docs/NEEDLE_TESTS.md)
+    for d in (48, 80, 96):
+        for tkv in (129, 513):
+            add("decode_narrow", "bf16", 8, 2, tkv, 4, 128, d=d, b=2)
+    for route in ("mx_hw", "mx_dequant"):
+        add(route, "mx", 8, 2, 2112, 4, 64, many=True)     # S=5, 64-key tail
+        add(route, "mx", 8, 2, 4160, 4, 64, many=True)     # S=9, 64-key tail
+        add(route, "mx", 2, 1, 2112, 8, 64, q_offset=1556, many=True,
+            note="frontier 1556..1563: a 21..28-key tail inside split 3, "
+                 "split 4 all-masked")
+    add("spec", "bf16", 4, 4, 2100, 17, 64, many=True)     # S=5 per chunk
+    # cache of capacity 4608 = nine 512-key splits: trailing splits are
+    # EMPTY by the live length, at positions below and at or above NG
+    for dt, tile in (("bf16", 64), ("fp8", 128)):
+        for live in (1, 513, 2048, 2049, 4097, 4608):
+            b = 2 if live in (2049, 4608) else 1
+            tq = min(4, live)
+            # 513 live keys leave a one-key second split: no choice of t2
+            fam = ("seam", "pair") if live >= 2048 else ("seam",)
+            cases.append(Case("cache", dt, 8, 2, live, tq, fam,
+                              pick_seams(live, tile, b * 8 * tq, 512), b=b,
+                              cap=4608, tile=tile))
+    # two shards of five splits each, the second with kv_offset = 2049
+    cuts2 = (0, 2049, 4150)
+    add("sharded", "bf16", 8, 2, 4150, 4, 64, cuts=cuts2, families=sf,
+        q_offset=3000, chunk=False, many=True,
+        seams=(512, 1024, 1536, 2048) + tuple(range(2561, 4150, 512)),
+        note="frontier 3000..3003 in the second shard; seams: the cut and "
+             "each shard's own split seams")
+
     ids = [c.id for c in cases]
     assert len(set(ids)) == len(ids), "duplicate case ids"
     return cases
@@ -403,6 +551,7 @@ class Needle:
     ref_q: torch.Tensor        # fp32 views the oracle sees
     ref_k: torch.Tensor
     ref_v: torch.Tensor
+    targets2: torch.Tensor | None = None   # `pair`: the second target
 
 
 def family_targets(case: Case, family: str) -> torch.Tensor:
@@ -414,13 +563,13 @@ def family_targets(case: Case, family: str) -> torch.Tensor:
     elif family == "first_masked":
         # a row whose first hidden key would lie past the KV keeps its diag
         tg = torch.where(pos + 1 < t, pos + 1, pos)
-    elif family in ("seam", "below"):
+    elif family in ("seam", "below", "pair"):   # pair: the FIRST target
         cand = seam_targets(case)
         tg = torch.empty(b, hq, tq, dtype=torch.long)
         for i in range(b):
             for h in range(hq):
                 for r in range(tq):
-                    c = cand if family == "seam" else \
+                    c = cand if family != "below" else \
                         [x for x in cand if x <= case.qoff + r]
                     # shift by one after every full cycle, so that the map
                     # is not symmetric under a (head, row) transposition;
@@ -513,6 +662,9 @@ def build_from(case: Case, family: str, k, v, mx, kf, vf) -> Needle:
     qdt = torch.float16 if case.dtype == "fp16" else torch.bfloat16
     q = qf.to(qdt)
     assert torch.equal(q.float(), qf), "gain*K must be exact in the query dtype"
+    tg2 = None
+    if family == "pair":
+        tg2, q = pair_query(case, tg, kf, gain, qdt)
     if family == "first_masked" and case.kind in ("fp8", "mx_hw"):
         # ANCHORED first-masked for the kernels that quantize P to e4m3: a
         # query on a hidden key alone leaves a diffuse softmax over the
@@ -549,7 +701,72 @@ def build_from(case: Case, family: str, k, v, mx, kf, vf) -> Needle:
         ref_q, ref_k, ref_v = q.float(), kf, vf
     causal = family in CAUSAL_FAMILIES
     return Needle(case, family, causal, case.qoff if causal else 0, 0,
-                  case.softmax_scale, tg, q, k, v, mx, ref_q, ref_k, ref_v)
+                  case.softmax_scale, tg, q, k, v, mx, ref_q, ref_k, ref_v, tg2)
+
+
+PAIR_NATS = (0.7, 1.5)   # |score(t1) - score(t2)| of a `pair` row
+
+
+def pair_query(case: Case, tg: torch.Tensor, kf: torch.Tensor, gain: float,
+               qdt: torch.dtype):
+    """The `pair` family: row r is gain * (K[t1] + K[t2]) with t1 the row's
+    seam target and t2 a key of the PARTNER split (split(t1) + ceil(S/2))
+    % S, S the splits that hold live keys. Each split's partial stays
+    one-hot (p = 1 in its own split, exact in e4m3), and the two partials
+    meet in the fp32 combine at weights between 0.82 / 0.18 and 0.67 / 0.33:
+    t2 is the key of the partner split that brings the two scores nearest
+    1.1 nats apart (brute force; a drawn t2 leaves a median minor weight of
+    0.04). The sum is rounded to the query dtype, for the e4m3-Q kinds to
+    e4m3 first (the anchored first_masked precedent); the oracle reads the
+    rounded query. -> (t2 (B, Hq, Tq), q)."""
+    s_live = case.live_splits
+    assert s_live >= 2, f"{case.id}: a pair needs two live splits"
+    g = case.hq // case.hkv
+    t2 = torch.empty_like(tg)
+    q = torch.empty(*tg.shape, case.d, dtype=qdt)
+    for i in range(case.b):
+        for h in range(case.hq):
+            for r in range(case.tq):
+                t2[i, h, r], q[i, h, r] = pair_key(
+                    kf[i, h // g, :case.tkv], int(tg[i, h, r]), s_live,
+                    case.plan[1], gain, case.softmax_scale,
+                    case.kind != "half", qdt, what=(case.id, i, h, r))
+    return t2, q
+
+
+def pair_key(keys: torch.Tensor, t1: int, s_live: int, chunk: int,
+             gain: float, scale: float, e4m3_q: bool, qdt: torch.dtype,
+             what=""):
+    """The second target of one `pair` row over `keys` (T, D) fp32, the live
+    keys of its KV head, and the row's query: -> (t2, q (D,) in qdt)."""
+    k1, kall = keys[t1], keys.double()
+    # a partner split of one or a few keys (the tail of 2049) may hold no
+    # key in range: then the next split serves
+    for step in range(s_live - 1):
+        sp = (t1 // chunk + (s_live + 1) // 2 + step) % s_live
+        if sp == t1 // chunk:
+            continue
+        lo, hi = sp * chunk, min((sp + 1) * chunk, keys.shape[0])
+        kc = keys[lo:hi]
+        qc = gain * (k1[None, :] + kc)
+        if e4m3_q:
+            qc = _e4m3(qc)
+        qc = qc.to(qdt)
+        s1 = (qc.double() * k1.double()).sum(-1) * scale
+        s2 = (qc.double() * kc.double()).sum(-1) * scale
+        nats = (s1 - s2).abs()
+        # nearest 1.1 nats first; a candidate whose sum query lifts a third
+        # key past 0.5 % of the weight (one row in 64 at 40000 keys) gives
+        # way to the next
+        for j in (nats - sum(PAIR_NATS) / 2).abs().argsort():
+            j = int(j)
+            if not PAIR_NATS[0] <= float(nats[j]) <= PAIR_NATS[1]:
+                break
+            sc = (kall @ qc[j].double()) * scale
+            two = torch.logsumexp(torch.stack([s1[j], s2[j]]), 0)
+            if float(torch.exp(two - torch.logsumexp(sc, 0))) >= 0.995:
+                return lo + j, qc[j]
+    raise AssertionError(f"no second target for {what}")
 
 
 @lru_cache(maxsize=None)
@@ -660,14 +877,19 @@ def oracle(q, k, v, *, causal=False, q_offset=0, kv_offset=0, scale=None,
         scale = 1.0 / math.sqrt(128)
     elif mutant not in (None, "gqa_mod", "batch_out_swap", "bh_transposed"):
         raise ValueError(mutant)
-    heads = torch.arange(hq)
-    kvh = heads % hkv if mutant == "gqa_mod" else heads // g
-    kk, vv = k[:, kvh], v[:, kvh]
-    tk = kk.shape[2]
+    tk = k.shape[2]
     if tk == 0:
         return (torch.zeros(b, hq, tq, d, dtype=torch.float64),
                 torch.full((b, hq, tq), float("-inf"), dtype=torch.float64))
-    s = torch.matmul(q, kk.transpose(-1, -2)) * scale
+    if mutant == "gqa_mod":
+        kvh = torch.arange(hq) % hkv
+        k, v, grp = k[:, kvh], v[:, kvh], 1
+    else:
+        grp = g     # head h reads KV head h // g: G heads share one matmul
+    # (B, Hq, Tq, .) <-> (B, Hq/grp, grp*Tq, .): K/V are never expanded
+    fold = lambda x: x.reshape(b, hq // grp, grp * tq, x.shape[-1])
+    s = torch.matmul(fold(q), k.transpose(-1, -2)).reshape(b, hq, tq, tk) \
+        * scale
     if causal:
         qpos = q_offset + torch.arange(tq)
         kpos = kv_offset + torch.arange(tk)
@@ -681,7 +903,7 @@ def oracle(q, k, v, *, causal=False, q_offset=0, kv_offset=0, scale=None,
     den = torch.where(den == 0, torch.ones_like(den), den)
     if p_round:
         p = _round_p(p, p_round)
-    out = torch.matmul(p, vv) / den
+    out = torch.matmul(fold(p), v).reshape(b, hq, tq, d) / den
     if mutant == "batch_out_swap":
         src = torch.arange(b) ^ 1
         src = torch.where(src < b, src, torch.arange(b))
@@ -744,6 +966,185 @@ def reference(case: Case, family: str):
     nd = build(case, family)
     return flash_res_lse(nd.ref_q, nd.ref_k, nd.ref_v, nd.scale, nd.causal,
                          nd.q_offset, nd.kv_offset)
+
+
+# --------------------------------------------------------------------------
+# fp64 split oracle: per-split partials by split_plan, merged by the stable
+# algebra; the split and combine errors are mutations of it
+# --------------------------------------------------------------------------
+SEAM_KEYS = 128    # seam_twice / seam_skipped move the first 128 keys
+
+
+def many_split_cases() -> list:
+    """The rows whose split-KV call has more than two splits."""
+    return [c for c in CASES if c.plan is not None and c.plan[0] > 2]
+
+
+def merge_partials(outs: torch.Tensor, lses: torch.Tensor):
+    """Stable merge over dim 0 in the dtype given: m = max lse, w =
+    exp(lse - m), out = sum w out / sum w, lse = m + log sum w; an all-masked
+    row gives out = 0, lse = -inf."""
+    m = lses.amax(0)
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    w = torch.exp(lses - m)              # exp(-inf) = 0 for a masked partial
+    den = w.sum(0)
+    safe = torch.where(den == 0, torch.ones_like(den), den)
+    out = (outs * w.unsqueeze(-1)).sum(0) / safe.unsqueeze(-1)
+    lse = torch.where(den == 0, torch.full_like(den, float("-inf")),
+                      m + torch.log(safe))
+    return out, lse
+
+
+@dataclass
+class SplitParts:
+    """fp64 partials of every split of a case's plan, each in two pieces:
+    `head` over the split's first SEAM_KEYS keys and `rest` over the others;
+    (S, B, Hq, Tq, D) and (S, B, Hq, Tq). A split past the live length is
+    empty: out = 0, lse = -inf."""
+    case: Case
+    head_o: torch.Tensor
+    head_l: torch.Tensor
+    rest_o: torch.Tensor
+    rest_l: torch.Tensor
+
+    def whole(self):
+        return merge_partials(torch.stack([self.head_o, self.rest_o]),
+                              torch.stack([self.head_l, self.rest_l]))
+
+
+def split_parts(nd: Needle, *, length: int | None = None, p_round=None,
+                q_round=None) -> SplitParts:
+    """Partials of nd over the splits of its case's plan. `length` cuts the
+    KV at another live length than the case's (cache rows): keys past the
+    case's own come from the guard pattern. p_round / q_round emulate the
+    kernel's arithmetic PER SPLIT, as the kernels round P against the
+    running max of their own split."""
+    c = nd.case
+    s_all, chunk = c.plan
+    k, v = nd.ref_k, nd.ref_v
+    n = c.tkv if length is None else length
+    if n > c.tkv:
+        gk, gv = guard_rows(nd, n)
+        k = torch.cat([k, gk[:, :, c.tkv:]], 2)
+        v = torch.cat([v, gv[:, :, c.tkv:]], 2)
+    pieces = ([], [], [], [])
+    for s in range(s_all):
+        lo, hi = s * chunk, min((s + 1) * chunk, n)
+        mid = min(lo + SEAM_KEYS, hi)
+        for j, (a, b) in enumerate(((lo, mid), (mid, hi))):
+            o, l = oracle(nd.ref_q, k[:, :, a:max(a, b)], v[:, :, a:max(a, b)],
+                          causal=nd.causal, q_offset=nd.q_offset,
+                          kv_offset=nd.kv_offset + a, scale=nd.scale,
+                          p_round=p_round, q_round=q_round)
+            pieces[2 * j].append(o)
+            pieces[2 * j + 1].append(l)
+    return SplitParts(c, *(torch.stack(p) for p in pieces))
+
+
+def split_oracle(nd: Needle, **kw):
+    """Attention through the split plan: per-split partials, merged."""
+    return merge_partials(*split_parts(nd, **kw).whole())
+
+
+def split_mutants(case: Case) -> list:
+    """The split and combine errors a many-split row must expose."""
+    s_live, chunk = case.live_splits, case.plan[1]
+    half = (s_live + 1) // 2
+    out = [("split_drop", s) for s in range(s_live)]
+    out += [("split_oswap", s, (s + half) % s_live) for s in range(s_live)
+            if s_live > 1]
+    if s_live > case.combine_groups:
+        out.append("combine_first_group")
+    if s_live > 1:
+        out += ["combine_mean", "lse_row_shift"]
+    if "pair" in case.families:
+        out.append("weight_base2")
+    # the seam mutants move the first keys of split s: seen where the row
+    # targets key s * chunk (every split seam, but for the 63-split rows,
+    # whose 64 rows reach the odd seams). Counting a one-hot key twice
+    # leaves `out` alone and adds ln 2 to lse, inside the lse bars of the
+    # e4m3-P kinds (5e-2 and 3e-2 of ~23): there the pair family sees it,
+    # and the one row of those kinds without one (fp8 cache, 513 live keys)
+    # cannot
+    named = [s for s in range(1, s_live) if s * chunk in case.seams]
+    if "pair" in case.families or case.kind not in ("fp8", "mx_hw"):
+        out += [("seam_twice", s) for s in named]
+    out += [("seam_skipped", s) for s in [0] + named]
+    if 0 < case.tkv - (s_live - 1) * chunk < case.tile and s_live > 1:
+        out.append("tail_split_empty")
+    if case.route == "cache" and case.tkv % chunk:
+        out += [("len_rounds_to_chunk", "down"), ("len_rounds_to_chunk", "up")]
+    return out
+
+
+def split_mutant(nd: Needle, parts: SplitParts, mut):
+    """(out, lse) of the split oracle with one error built in:
+
+    ("split_drop", s)         split s never reaches the combine
+    ("split_oswap", s, t)     out partials of s and t exchanged, lse kept
+    "combine_first_group"     only the first NG splits reduced (NG of
+                              fa_combine_kernel: 4, or 8 at D = 64)
+    "combine_mean"            unweighted mean of the non-empty out partials,
+                              final lse right
+    "weight_base2"            w = 2^(l - m), final lse right
+    "lse_row_shift"           weights of row r taken from row r ^ 1, final
+                              lse right
+    ("seam_twice", s)         the first 128 keys of split s also counted in
+                              split s - 1
+    ("seam_skipped", s)       ... counted in neither
+    "tail_split_empty"        a last split shorter than one tile dropped
+    ("len_rounds_to_chunk", "down" | "up")
+                              live length rounded to a chunk boundary (up:
+                              into the guard pattern)
+    """
+    c = nd.case
+    name = mut if isinstance(mut, str) else mut[0]
+    if name == "len_rounds_to_chunk":
+        chunk = c.plan[1]
+        n = c.tkv // chunk * chunk + (chunk if mut[1] == "up" else 0)
+        return split_oracle(nd, length=n)
+    o, l = parts.whole()
+    true_out, true_lse = merge_partials(o, l)
+    if name == "split_drop" or name == "tail_split_empty":
+        s = mut[1] if name == "split_drop" else c.live_splits - 1
+        keep = [i for i in range(o.shape[0]) if i != s]
+        return merge_partials(o[keep], l[keep])
+    if name == "split_oswap":
+        idx = list(range(o.shape[0]))
+        idx[mut[1]], idx[mut[2]] = mut[2], mut[1]
+        return merge_partials(o[idx], l)
+    if name == "combine_first_group":
+        ng = c.combine_groups
+        return merge_partials(o[:ng], l[:ng])
+    if name == "seam_twice":
+        s = mut[1]
+        o, l = o.clone(), l.clone()
+        o[s - 1], l[s - 1] = merge_partials(
+            torch.stack([o[s - 1], parts.head_o[s]]),
+            torch.stack([l[s - 1], parts.head_l[s]]))
+        return merge_partials(o, l)
+    if name == "seam_skipped":
+        s = mut[1]
+        o, l = o.clone(), l.clone()
+        o[s], l[s] = parts.rest_o[s], parts.rest_l[s]
+        return merge_partials(o, l)
+    # the weight mutants: the final lse stays right
+    m = l.amax(0)
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    if name == "combine_mean":
+        w = torch.isfinite(l).double()
+    elif name == "weight_base2":
+        w = torch.exp2(l - m)
+    elif name == "lse_row_shift":
+        flat = torch.exp(l - m).reshape(l.shape[0], -1)
+        src = torch.arange(flat.shape[1]) ^ 1
+        src = torch.where(src < flat.shape[1], src, src ^ 1)
+        w = flat[:, src].reshape(l.shape)
+    else:
+        raise ValueError(mut)
+    den = w.sum(0)
+    den = torch.where(den == 0, torch.ones_like(den), den)
+    return (o * w.unsqueeze(-1)).sum(0) / den.unsqueeze(-1), true_lse
 
 
 # --------------------------------------------------------------------------
@@ -835,11 +1236,12 @@ def run_kernel(nd: Needle, use_guard: bool = False):
     return flash.local_attention(q, k, v, *args)
 
 
-def cache_buffers(nd: Needle, cap: int = CACHE_CAP):
-    """(B, Hkv, cap, D) K/V caches: the needle's keys as the live prefix,
-    the guard pattern (decoy K, NaN V) in every row at and past it."""
+def cache_buffers(nd: Needle):
+    """(B, Hkv, capacity, D) K/V caches: the needle's keys as the live
+    prefix, the guard pattern (decoy K, NaN V) in every row at and past
+    it."""
     c = nd.case
-    gk, gv = guard_rows(nd, cap)
+    gk, gv = guard_rows(nd, c.capacity)
     kc, vc = gk.to(nd.k.dtype).cuda(), gv.to(nd.v.dtype).cuda()
     kc[:, :, :c.tkv] = nd.k.cuda()
     vc[:, :, :c.tkv] = nd.v.cuda()

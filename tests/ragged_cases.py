@@ -9,8 +9,12 @@ row at or past a row's length holds a decoy K and a NaN V, so a length one
 long (or another row's longer length) poisons the output. A row of length 0
 must come back as out = 0, lse = -inf.
 
+One more length set, (4097, 0, 513, 2560), runs at a capacity of 4608 (nine
+512-key splits): its rows leave none, all, seven and four trailing splits
+empty, and their heads target the first key of every live split they reach.
+
 This module is a plain helper (not a conftest). K/V are drawn once per dtype
-and shared, unchanged, by every length set and test.
+and capacity and shared, unchanged, by every length set and test.
 """
 
 from __future__ import annotations
@@ -30,6 +34,13 @@ LENGTH_SETS = (
     (1, 65, 512, 1024),
     (511, 129, 127, 1000),
 )
+# a second capacity, 4608 = nine 512-key splits: row 0 fills all nine (the
+# last with one key), row 1 is empty, row 2 leaves splits 2..8 empty and row
+# 3 splits 5..8 (empty trailing splits below and at or above the combine
+# kernel's group count of 4)
+CAP_BIG = 4608
+LENGTH_SETS_BIG = ((4097, 0, 513, 2560),)
+CHUNK = 512    # needle_cases.split_plan(4, 2, cap)[1] for both capacities
 DTYPES = ("bf16", "fp8")
 KIND = {"bf16": "half", "fp8": "fp8"}
 SEAMS = (0, 63, 64, 127, 128, 511, 512)
@@ -44,12 +55,18 @@ GRAPH_STEPS = tuple(
 _TD = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}
 
 
+def cap_of(lengths) -> int:
+    """The cache capacity a length set runs at."""
+    return CAP_BIG if tuple(lengths) in LENGTH_SETS_BIG else CAP
+
+
 @dataclass
 class Ragged:
     lengths: tuple
     dtype: str
     kind: str
-    k: torch.Tensor         # (B, Hkv, CAP, D) storage dtype; row b's live
+    cap: int
+    k: torch.Tensor         # (B, Hkv, cap, D) storage dtype; row b's live
     v: torch.Tensor         # keys are [:lengths[b]]
     q: torch.Tensor         # (B, Hq, 1, D) bf16
     targets: torch.Tensor   # (B, Hq) key each head attends; -1: empty row
@@ -57,35 +74,42 @@ class Ragged:
     v_cache: torch.Tensor   # row's length
     ref_out: torch.Tensor   # fp32 oracle (B, Hq, 1, D)
     ref_lse: torch.Tensor   # (B, Hq, 1); -inf for an empty row
+    targets2: torch.Tensor | None = None   # family "pair": the second target
 
 
 @lru_cache(maxsize=None)
-def kv(dtype: str):
-    """randn rounded to the cache dtype, every batch row different."""
-    g = torch.Generator().manual_seed(SEED)
-    k = torch.randn(B, HKV, CAP, D, generator=g).to(_TD[dtype])
-    v = torch.randn(B, HKV, CAP, D, generator=g).to(_TD[dtype])
+def kv(dtype: str, cap: int = CAP):
+    """randn rounded to the cache dtype, every batch row different; one
+    draw per capacity."""
+    g = torch.Generator().manual_seed(SEED + (cap if cap != CAP else 0))
+    k = torch.randn(B, HKV, cap, D, generator=g).to(_TD[dtype])
+    v = torch.randn(B, HKV, cap, D, generator=g).to(_TD[dtype])
     return k, v
 
 
 def targets(lengths) -> torch.Tensor:
     """Head 0 of every row targets L_b - 1; the other heads rotate, offset
-    by b, over L_b - 1 and the seams below L_b."""
+    by b, over L_b - 1 and the seams below L_b. At the capacity of nine
+    splits the seams are the first keys of the row's live splits, last split
+    first (eight heads: row 0 reaches splits 8..1, rows 2 and 3 every live
+    split)."""
     tg = torch.full((B, HQ), -1, dtype=torch.long)
+    big = cap_of(lengths) == CAP_BIG
     for b, n in enumerate(lengths):
         if n == 0:
             continue
-        cand = [n - 1] + [s for s in SEAMS if s < n and s != n - 1]
+        seams = reversed(range(0, n, CHUNK)) if big else SEAMS
+        cand = [n - 1] + [s for s in seams if s < n and s != n - 1]
         tg[b, 0] = n - 1
         for h in range(1, HQ):
             tg[b, h] = cand[(h + b) % len(cand)]
     return tg
 
 
-def guard_fill(q: torch.Tensor):
-    """(B, Hkv, CAP, D) fp32 guard rows: decoy K = twice a query of that KV
+def guard_fill(q: torch.Tensor, cap: int = CAP):
+    """(B, Hkv, cap, D) fp32 guard rows: decoy K = twice a query of that KV
     head's group (rotating), V = NaN."""
-    j = torch.arange(CAP)
+    j = torch.arange(cap)
     heads = torch.arange(HKV)[:, None] * G + (j % G)[None, :]    # (Hkv, CAP)
     gk = 2.0 * q.float()[:, heads, 0]                     # (B, Hkv, CAP, D)
     return gk, torch.full_like(gk, float("nan"))
@@ -94,8 +118,8 @@ def guard_fill(q: torch.Tensor):
 def write_guards(k, v, q, lengths) -> None:
     """Overwrite, IN PLACE, every row of k / v (B, Hkv, cap, D) at or past
     lengths[b] with the guard pattern (any device, the tensors' dtype)."""
-    gk, gv = guard_fill(q.cpu())
     cap = k.shape[2]
+    gk, gv = guard_fill(q.cpu(), cap)
     for b, n in enumerate(lengths):
         k[b, :, n:] = gk[b, :, n:cap].to(device=k.device, dtype=k.dtype)
         v[b, :, n:] = gv[b, :, n:cap].to(device=v.device, dtype=v.dtype)
@@ -110,11 +134,11 @@ def with_guards(k, v, q, lengths):
 
 def attend_lengths(rg: "Ragged", lengths, fn):
     """Row-by-row attention over the GUARDED cache with row b cut at
-    lengths[b] (clipped to [0, CAP]): the true lengths give the oracle, any
-    other lengths a mutant. fn(q, k, v) -> (out, lse)."""
+    lengths[b] (clipped to [0, capacity]): the true lengths give the oracle,
+    any other lengths a mutant. fn(q, k, v) -> (out, lse)."""
     outs, lses = [], []
     for b, n in enumerate(lengths):
-        n = max(0, min(int(n), CAP))
+        n = max(0, min(int(n), rg.cap))
         qb = rg.q[b:b + 1].float()
         if n == 0:
             outs.append(torch.zeros(1, HQ, 1, D))
@@ -128,10 +152,16 @@ def attend_lengths(rg: "Ragged", lengths, fn):
 
 
 @lru_cache(maxsize=None)
-def build(lengths: tuple, dtype: str) -> Ragged:
+def build(lengths: tuple, dtype: str, family: str = "seam") -> Ragged:
+    """family "pair" (the nine-split capacity): every head of a row with at
+    least three live splits reads 2 * (K[t1] + K[t2]), t1 its seam target
+    and t2 a key of the partner split chosen by needle_cases.pair_key, so
+    the combine weighs two live splits at 0.67..0.82 / 0.18..0.33; the other
+    rows keep their one-hot query. rg.targets2 holds t2 (-1: none)."""
     from tree_attention_torch_amd.ops.reference import flash_res_lse
 
-    k, v = kv(dtype)
+    cap = cap_of(lengths)
+    k, v = kv(dtype, cap)
     tg = targets(lengths)
     kvh = torch.arange(HQ) // G
     bi = torch.arange(B)[:, None]
@@ -141,9 +171,21 @@ def build(lengths: tuple, dtype: str) -> Ragged:
     qf = nc.needle_gain(D) * k.float()[bi, kvh[None, :], idx]    # (B, Hq, D)
     q = qf.to(torch.bfloat16)[:, :, None, :].contiguous()
     assert torch.equal(q.float()[:, :, 0], qf), "gain*K must be exact in bf16"
+    tg2 = torch.full_like(tg, -1)
+    if family == "pair":
+        assert cap == CAP_BIG
+        for b, n in enumerate(lengths):
+            live = -(-n // CHUNK)
+            for h in range(HQ if live >= 3 else 0):
+                tg2[b, h], q[b, h, 0] = nc.pair_key(
+                    k[b, h // G, :n].float(), int(tg[b, h]), live, CHUNK,
+                    nc.needle_gain(D), 1.0 / D ** 0.5, dtype == "fp8",
+                    torch.bfloat16, what=(lengths, dtype, b, h))
+    else:
+        assert family == "seam", family
     k_cache, v_cache = with_guards(k, v, q, lengths)
-    rg = Ragged(tuple(lengths), dtype, KIND[dtype], k, v, q, tg, k_cache,
-                v_cache, None, None)
+    rg = Ragged(tuple(lengths), dtype, KIND[dtype], cap, k, v, q, tg, k_cache,
+                v_cache, None, None, tg2)
     rg.ref_out, rg.ref_lse = attend_lengths(rg, lengths, flash_res_lse)
     return rg
 
@@ -156,8 +198,16 @@ def mutant_lengths(lengths) -> dict:
         "L-1": [x - 1 for x in n],
         "row0_for_all": [n[0]] * B,
         "max_for_all": [max(n)] * B,
-        "capacity_for_all": [CAP] * B,
+        "capacity_for_all": [cap_of(lengths)] * B,
         "row_b^1": [n[b ^ 1] for b in range(B)],
+    }
+
+
+def chunk_mutant_lengths(lengths) -> dict:
+    """The live length rounded to a boundary of the 512-key split chunk."""
+    return {
+        "chunk_down": [x // CHUNK * CHUNK for x in lengths],
+        "chunk_up": [-(-x // CHUNK) * CHUNK for x in lengths],
     }
 
 

@@ -6,6 +6,9 @@ reduction AND doubles as the race detector for the collective path,
 SURVEY.md §5.2), and robust to -inf LSEs from fully-masked shards.
 """
 
+import math
+
+import pytest
 import torch
 
 from tree_attention_torch_amd.ops.reference import flash_res_lse
@@ -146,3 +149,55 @@ def test_combine_partials_all_empty():
     out, lse = combine_partials(outs, lses)
     assert torch.isfinite(out).all() and (out == 0).all()
     assert torch.isinf(lse).all() and (lse < 0).all()
+
+
+# --------------------------------------------------------------------------
+# the contents the HIP combine kernels are run on (tests/test_gpu_combine.py)
+# against the fp64 formula, here through the two eager forms
+# --------------------------------------------------------------------------
+def _allreduce_eager(outs, lses):
+    """tree_combine_allreduce without a process group: every split is a
+    rank, the MAX all-reduce an elementwise max of what allreduce_local_max
+    offers, the SUM all-reduce a sum of the eager packs."""
+    from tree_attention_torch_amd.parallel import combine as cb
+
+    m = torch.stack([cb.allreduce_local_max(l) for l in lses]).amax(0)
+    packed = sum(cb._pack_eager(o, l, m) for o, l in zip(outs, lses))
+    return cb._finish_eager(packed, m)
+
+
+def _combine_partials_rows(outs, lses):
+    s, rows, d = outs.shape
+    out, lse = combine_partials(outs.reshape(s, 1, rows, 1, d),
+                                lses.reshape(s, 1, rows, 1))
+    return out.reshape(rows, d), lse.reshape(rows)
+
+
+@pytest.mark.parametrize("s", (1, 2, 3, 5, 8, 9, 17))
+def test_eager_combines_equal_fp64_formula(s):
+    import combine_cases as cc
+
+    for rows in (1, 105):
+        for name, outs, lses, exact in cc.contents(s, rows, 32, ng=4):
+            if name.startswith("one_finite"):
+                cc.one_finite_is_exact(outs, lses)
+            cc.check(name, *_combine_partials_rows(outs, lses), outs, lses,
+                     exact, "combine_partials")
+            cc.check(name, *_allreduce_eager(outs, lses), outs, lses, exact,
+                     "eager all-reduce combine")
+
+
+def test_allreduce_very_negative_lse_with_masked_peer():
+    """One rank fully masked, the others at lse = -200: the all-reduce path
+    must return lse = -200 + log(n), as combine_partials does. With -80 as
+    the masked rank's stand-in in the MAX all-reduce it returned -160."""
+    outs = torch.randn(3, 4, 16, generator=torch.Generator().manual_seed(5))
+    lses = torch.full((3, 4), -200.0)
+    lses[1] = float("-inf")
+    want = -200.0 + math.log(2.0)
+    for out, lse in (_combine_partials_rows(outs, lses),
+                     _allreduce_eager(outs, lses)):
+        torch.testing.assert_close(lse, torch.full((4,), want),
+                                   rtol=1e-5, atol=1e-5)
+        torch.testing.assert_close(out, (outs[0] + outs[2]) / 2,
+                                   rtol=1e-5, atol=1e-5)

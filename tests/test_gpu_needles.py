@@ -8,6 +8,17 @@ a batch index dropped from a KV base, exchanged in an output offset or decoded
 transposed with the head; every row with a softmax scale of its own a kernel
 that ignores it.
 
+The many-split rows (S = 3 .. 63 splits: 1100 .. 8193 keys, and two rows
+of 40000) put a needle in every split and on both sides of every split seam,
+and their `pair` family puts two targets in different splits at weights
+0.67..0.82 / 0.18..0.33, so the combine must weigh two live splits right;
+on the CPU they reject a dropped split, out partials exchanged, a combine
+that stops after its first group of splits, an unweighted mean, base-2
+weights, weights from the neighbouring row, a seam counted twice or not at
+all, and a live length rounded to a chunk. The seams come from
+needle_cases.split_plan, which mirrors the binding's split heuristic with
+TREE_ATTN_SPLIT_BLOCKS unset: the `ext` fixture asserts that it is.
+
 Each query row is gain * K[target], so `out` names the key that was read.
 A failure prints the worst row's target key, the nearest seam and the family
 (docs/NEEDLE_TESTS.md lists which seams each kernel has).
@@ -49,6 +60,7 @@ def ext():
     from tree_attention_torch_amd.ops import flash
 
     assert flash.hip_available(), "HIP extension must be built in-tree"
+    nc.assert_default_split_plan()
     return flash._load_extension()
 
 
@@ -78,14 +90,16 @@ _CACHE = [c for c in nc.CASES if c.route == "cache"]
 @pytest.mark.parametrize("case", _CACHE, ids=[c.id for c in _CACHE])
 def test_needle_cache(ext, case):
     """ext.flash_attention_cache: live length from device memory over a
-    cap-1024 cache whose every row at and past the live length holds the
-    guard pattern. One row read past the live length is a NaN (or a decoy
-    that outscores the needle 4x), not 1/T of extra weight."""
-    nd = nc.build(case, "seam")
-    out, lse = nc.run_cache(nd)
-    assert torch.isfinite(out).all() and torch.isfinite(lse).all(), \
-        f"{case.id}: guard rows past live length {case.tkv} leaked"
-    nc.check(nd, out, lse, f"cache live={case.tkv}")
+    cache of capacity 1024 (two splits) or 4608 (nine: the trailing ones
+    empty by the live length) whose every row at and past the live length
+    holds the guard pattern. One row read past the live length is a NaN (or
+    a decoy that outscores the needle 4x), not 1/T of extra weight."""
+    for fam in case.families:
+        nd = nc.build(case, fam)
+        out, lse = nc.run_cache(nd)
+        assert torch.isfinite(out).all() and torch.isfinite(lse).all(), \
+            f"{case.id}: guard rows past live length {case.tkv} leaked"
+        nc.check(nd, out, lse, f"cache live={case.tkv}")
 
 
 def test_needle_cache_graph_replay(ext):

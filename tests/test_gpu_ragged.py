@@ -22,6 +22,12 @@ def ext():
     return flash._load_extension()
 
 
+# capacity 1024, then 4608 with its seam and its pair family
+SETS = [pytest.param(n, "seam", id=str(n))
+        for n in rc.LENGTH_SETS + rc.LENGTH_SETS_BIG] + \
+    [pytest.param(n, "pair", id=f"{n}-pair") for n in rc.LENGTH_SETS_BIG]
+
+
 def _len_dev(lengths):
     return torch.tensor(list(lengths), dtype=torch.long, device="cuda")
 
@@ -30,9 +36,15 @@ def _len_dev(lengths):
 # flash_attention_cache with one length per batch row
 # --------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", rc.DTYPES)
-@pytest.mark.parametrize("lengths", rc.LENGTH_SETS, ids=str)
-def test_cache_kernel_per_row_lengths(ext, lengths, dtype):
-    rg = rc.build(lengths, dtype)
+@pytest.mark.parametrize("lengths,family", SETS)
+def test_cache_kernel_per_row_lengths(ext, lengths, family, dtype):
+    """Capacity 1024 (two splits) and 4608 (nine: rows of 4097, 0, 513 and
+    2560 keys leave none, all, seven and four trailing splits empty)."""
+    import needle_cases as nc
+
+    nc.assert_default_split_plan()
+    rg = rc.build(lengths, dtype, family)
+    assert rg.k_cache.shape[2] == rc.cap_of(lengths)
     out, lse = ext.flash_attention_cache(
         rg.q.cuda(), rg.k_cache.cuda(), rg.v_cache.cuda(), _len_dev(lengths),
         1.0 / rc.D ** 0.5)
@@ -138,12 +150,13 @@ def test_kv_cache_append_checks(ext):
 # --------------------------------------------------------------------------
 # RaggedDecodeSession
 # --------------------------------------------------------------------------
-def _session(dtype, **kw):
+def _session(dtype, cap=rc.CAP, **kw):
     from tree_attention_torch_amd.session import RaggedDecodeSession
 
-    sess = RaggedDecodeSession(rc.B, rc.HKV, rc.D, max_tokens=768,
+    # capacity = (ceil(max_tokens / block) + 1) blocks: 1024 or 4608
+    sess = RaggedDecodeSession(rc.B, rc.HKV, rc.D, max_tokens=cap - 256,
                                device="cuda", kv_dtype=dtype, block=256, **kw)
-    assert sess.capacity == rc.CAP
+    assert sess.capacity == cap
     return sess
 
 
@@ -156,7 +169,7 @@ def _feed(sess, rg, lengths, tail=3):
             sess.prefill(b, ks[b, :, :n - tail], vs[b, :, :n - tail])
     while sess.totals != list(lengths):
         mask = [sess.totals[b] < lengths[b] for b in range(rc.B)]
-        at = torch.tensor(sess.totals).clamp(max=rc.CAP - 1)
+        at = torch.tensor(sess.totals).clamp(max=rg.cap - 1)
         bi = torch.arange(rc.B)
         sess.append(ks[bi, :, at][:, :, None], vs[bi, :, at][:, :, None],
                     mask)
@@ -172,10 +185,10 @@ def _guard(sess, rg, lengths):
 
 
 @pytest.mark.parametrize("dtype", rc.DTYPES)
-@pytest.mark.parametrize("lengths", rc.LENGTH_SETS, ids=str)
-def test_ragged_session_gpu(ext, lengths, dtype):
-    rg = rc.build(lengths, dtype)
-    sess = _session(dtype)
+@pytest.mark.parametrize("lengths,family", SETS)
+def test_ragged_session_gpu(ext, lengths, family, dtype):
+    rg = rc.build(lengths, dtype, family)
+    sess = _session(dtype, rg.cap)
     _feed(sess, rg, lengths)
     for b, n in enumerate(lengths):   # stored bytes are the ones .to() gives
         assert torch.equal(sess.k[b, :, :n].cpu().view(torch.uint8),

@@ -182,6 +182,49 @@ def test_uneven_shards_ws2():
     assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
 
 
+def _worker_allreduce_masked_peer(rank, world_size, port):
+    import torch.distributed as dist
+
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    os.environ["RANK"] = str(rank)
+    dist.init_process_group("gloo", rank=rank, world_size=world_size)
+    try:
+        from tree_attention_torch_amd.parallel.combine import (
+            combine_partials, tree_combine_allgather, tree_combine_allreduce)
+
+        # both ranks draw both partials; rank 1 is fully masked on row 0,
+        # rank 0 on row 1, and every finite lse lies in [-250, -150]
+        g = torch.Generator().manual_seed(13)
+        outs = torch.randn(2, 1, 4, 3, 16, generator=g)
+        lses = -250.0 + 100.0 * torch.rand(2, 1, 4, 3, generator=g)
+        lses[1, :, :, 0] = float("-inf")
+        lses[0, :, :, 1] = float("-inf")
+        want_out, want_lse = combine_partials(outs, lses)
+        assert float(want_lse.max()) < -149.0
+        for fn in (tree_combine_allreduce, tree_combine_allgather):
+            out, lse = fn(outs[rank], lses[rank])
+            torch.testing.assert_close(lse, want_lse, rtol=1e-5, atol=1e-5)
+            torch.testing.assert_close(out, want_out, rtol=1e-5, atol=1e-5)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_allreduce_very_negative_lse_with_masked_peer_ws2():
+    """A masked rank must not raise the running max of the all-reduce
+    combine: with lse = -200 beside a masked peer it returned lse = -160
+    while the all-gather path returned -200."""
+    _PORT[0] += 1
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=_worker_allreduce_masked_peer,
+                         args=(r, 2, _PORT[0])) for r in range(2)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(timeout=120)
+    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+
+
 def _worker_mx(rank, world_size, port):
     import torch.distributed as dist
 

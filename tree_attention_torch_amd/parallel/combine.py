@@ -44,6 +44,12 @@ __all__ = [
 # below ~exp(-80) a shard's contribution underflows fp32 relative to the max;
 # clamping keeps exp() finite when a fully-masked shard reports lse = -inf.
 _NEG_CLAMP = -80.0
+# what a fully-masked rank offers the MAX all-reduce in place of -inf: finite
+# (so lse - m is never inf - inf) and below every reachable lse, so it never
+# becomes the running max of a row another rank has keys for. The HIP combine
+# kernels read any lse <= -1e30 as masked. (It was -80 once: a row whose live
+# ranks all sat below that, lse = -200 say, came back as lse = -160.)
+_MASKED_LSE = -1e30
 
 
 def auto_strategy(out_numel: int) -> str:
@@ -58,6 +64,32 @@ def _rescale(out: torch.Tensor, lse: torch.Tensor, m: torch.Tensor):
     w = torch.exp(torch.clamp(lse - m, min=_NEG_CLAMP, max=0.0))
     w = torch.where(torch.isfinite(lse), w, torch.zeros_like(w))
     return out * w.unsqueeze(-1), w
+
+
+def _pack_eager(out: torch.Tensor, lse: torch.Tensor, m: torch.Tensor):
+    """[num || den], the operand of the SUM all-reduce (the eager twin of the
+    combine_rescale_pack kernel)."""
+    num, den = _rescale(out, lse, m)
+    return torch.cat([num, den.unsqueeze(-1)], dim=-1).contiguous()
+
+
+def _finish_eager(packed: torch.Tensor, m: torch.Tensor):
+    """(out, lse) from the summed [num || den] and the global max (the eager
+    twin of the combine_finish kernel)."""
+    num_g = packed[..., :-1]
+    den_g = packed[..., -1]
+    den_safe = torch.where(den_g == 0, torch.ones_like(den_g), den_g)
+    out_g = num_g / den_safe.unsqueeze(-1)
+    lse_g = m + torch.log(den_safe)
+    lse_g = torch.where(den_g == 0, torch.full_like(lse_g, float("-inf")), lse_g)
+    return out_g, lse_g
+
+
+def allreduce_local_max(lse: torch.Tensor) -> torch.Tensor:
+    """This rank's operand of tree_combine_allreduce's MAX all-reduce: its
+    lse, with _MASKED_LSE where the rank is fully masked (lse = -inf)."""
+    return torch.where(torch.isfinite(lse), lse,
+                       torch.full_like(lse, _MASKED_LSE))
 
 
 def combine_partials(
@@ -104,7 +136,7 @@ def tree_combine_allreduce(
     """
     out = out.float().contiguous()
     lse = lse.float().contiguous()
-    m = torch.where(torch.isfinite(lse), lse, torch.full_like(lse, _NEG_CLAMP))
+    m = allreduce_local_max(lse)
     dist.all_reduce(m, op=dist.ReduceOp.MAX, group=group)
     b, h, tq, d = out.shape
     ext = None
@@ -117,21 +149,13 @@ def tree_combine_allreduce(
         # exp/clamp/where/mul/cat chain (67 MB per 4096-row prefill chunk)
         packed = ext.combine_rescale_pack(out, lse.contiguous(), m.contiguous())
     else:
-        num, den = _rescale(out, lse, m)
-        packed = torch.cat([num.reshape(b, h, tq, d), den.unsqueeze(-1)], dim=-1)
-        packed = packed.contiguous()
+        packed = _pack_eager(out, lse, m)
     work = dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group, async_op=async_op)
 
     def _finish():
         if ext is not None:
             return ext.combine_finish(packed, m.contiguous())
-        num_g = packed[..., :d]
-        den_g = packed[..., d]
-        den_safe = torch.where(den_g == 0, torch.ones_like(den_g), den_g)
-        out_g = num_g / den_safe.unsqueeze(-1)
-        lse_g = m + torch.log(den_safe)
-        lse_g = torch.where(den_g == 0, torch.full_like(lse_g, float("-inf")), lse_g)
-        return out_g, lse_g
+        return _finish_eager(packed, m)
 
     if async_op:
         class _Handle:
