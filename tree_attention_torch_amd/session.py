@@ -29,7 +29,7 @@ import torch.distributed as dist
 from .ops.flash import local_attention
 from .parallel.combine import combine_partials, tree_combine
 
-__all__ = ["DecodeSession", "RaggedDecodeSession"]
+__all__ = ["DecodeSession", "RaggedDecodeSession", "PagedDecodeSession"]
 
 _DTYPES = {
     "bf16": torch.bfloat16,
@@ -428,13 +428,24 @@ class RaggedDecodeSession:
         block: int = 256,
         group: dist.ProcessGroup | None = None,
     ) -> None:
+        td, local_cap = self._setup(batch, max_tokens, device, kv_dtype,
+                                    block, group)
+        self.k = torch.empty(batch, kv_heads, local_cap, head_dim, dtype=td,
+                             device=self.device)
+        self.v = torch.empty_like(self.k)
+
+    def _setup(self, batch, max_tokens, device, kv_dtype, block, group):
+        """Everything but the KV storage: rank and world, the lengths on
+        host and device. Returns (storage dtype, positions per row that
+        max_tokens asks of this rank's shard)."""
+        name = type(self).__name__
         if isinstance(kv_dtype, str) and kv_dtype in ("mx", "fp8_mx"):
             raise ValueError(
-                "RaggedDecodeSession: the MX cache keeps host-side window "
+                f"{name}: the MX cache keeps host-side window "
                 "state per sequence and is not supported; use bf16, fp16, "
                 "fp32 or fp8")
         if isinstance(kv_dtype, str) and kv_dtype not in _DTYPES:
-            raise ValueError(f"RaggedDecodeSession: unknown kv_dtype "
+            raise ValueError(f"{name}: unknown kv_dtype "
                              f"{kv_dtype!r}")
         self.device = torch.device(device)
         if dist.is_available() and dist.is_initialized():
@@ -448,15 +459,13 @@ class RaggedDecodeSession:
         blocks_total = (max_tokens + block - 1) // block + 1
         local_cap = ((blocks_total + self.world - 1) // self.world) * block
         td = _DTYPES[kv_dtype] if isinstance(kv_dtype, str) else kv_dtype
-        self.k = torch.empty(batch, kv_heads, local_cap, head_dim, dtype=td,
-                             device=self.device)
-        self.v = torch.empty_like(self.k)
         self.total_dev = torch.zeros(batch, dtype=torch.long,
                                      device=self.device)
         self.local_len_dev = torch.zeros_like(self.total_dev)
         self.totals = [0] * batch       # global tokens of each sequence
         self.local_lens = [0] * batch   # of them, in THIS rank's shard
         self._mask_cache: dict[tuple, torch.Tensor] = {}
+        return td, local_cap
 
     # ---- host mirror ----
     @property
@@ -520,14 +529,14 @@ class RaggedDecodeSession:
     def _append_kernel_ok(self) -> bool:
         return self.device.type == "cuda" and self._row_bytes % 4 == 0
 
-    @staticmethod
-    def _ext():
+    @classmethod
+    def _ext(cls):
         from .ops.flash import _load_extension
 
         ext = _load_extension()
         if ext is None:
             raise RuntimeError(
-                "RaggedDecodeSession: the gfx950 HIP extension "
+                f"{cls.__name__}: the gfx950 HIP extension "
                 "_tree_attn_hip is not built but the session is on a GPU")
         return ext
 
@@ -689,6 +698,307 @@ class RaggedDecodeSession:
         def replay(active=None) -> torch.Tensor:
             mask = self._mask(active)
             self._check_capacity(mask)
+            self._advance(mask)
+            if mask != in_buffer[0]:   # a steady mask costs no copy at all
+                active_dev.copy_(self._mask_dev(mask))
+                in_buffer[0] = mask
+            graph.replay()
+            if self.world == 1:
+                return out_l
+            out, _ = tree_combine(out_l, lse_l, strategy=combine,
+                                  group=self.group)
+            return out
+
+        return replay
+
+
+# --------------------------------------------------------------------------
+# ragged batch over a paged pool: memory follows the live lengths
+# --------------------------------------------------------------------------
+_PAGE_SIZES = (128, 256, 512, 1024)
+
+
+class PagedDecodeSession(RaggedDecodeSession):
+    """RaggedDecodeSession over a page pool instead of a (B, Hkv, capacity,
+    D) slab: same surface, same block-cyclic sharding, same lengths on host
+    and device, but a sequence holds only the pages its live length needs.
+
+    ``k_pool`` / ``v_pool`` are (n_pages, Hkv, page, D) and ``page_table``
+    is (B, max_pages) int32 on the device: entry [b, j] is the physical page
+    of local positions [j * page, (j + 1) * page) of sequence b on this
+    rank's shard (ops/hip/ta_abi.h PageArgs). ``max_tokens`` is the
+    per-sequence ceiling and fixes the table's width; ``pool_tokens`` sizes
+    this rank's pool for all sequences together.
+
+    Pages come from a host-side free list. The host mirror of the lengths is
+    exact, so before each step the host knows which rows land on a new page:
+    it takes the page and writes that one table entry with a stream-ordered
+    device fill (no pageable host-to-device copy, no device-side
+    allocation). reset(b) hands row b's pages back. A pool that runs out and
+    a row at its ceiling both raise RuntimeError naming the row, before
+    anything is launched or stored.
+    """
+
+    def __init__(
+        self,
+        batch: int,
+        kv_heads: int,
+        head_dim: int,
+        max_tokens: int,
+        pool_tokens: int,
+        page: int = 256,
+        device: torch.device | str = "cuda",
+        kv_dtype: str | torch.dtype = "bf16",
+        block: int = 256,
+        group: dist.ProcessGroup | None = None,
+    ) -> None:
+        if page not in _PAGE_SIZES:
+            raise ValueError(f"PagedDecodeSession: page must be one of "
+                             f"{_PAGE_SIZES}, got {page!r}")
+        td, local_cap = self._setup(batch, max_tokens, device, kv_dtype,
+                                    block, group)
+        self._page = page
+        max_pages = (local_cap + page - 1) // page
+        n_pages = max(1, (pool_tokens + page - 1) // page)
+        self.k_pool = torch.empty(n_pages, kv_heads, page, head_dim, dtype=td,
+                                  device=self.device)
+        self.v_pool = torch.empty_like(self.k_pool)
+        # entries past a row's live pages are never read
+        self.page_table = torch.zeros(batch, max_pages, dtype=torch.int32,
+                                      device=self.device)
+        self._pages: list[list[int]] = [[] for _ in range(batch)]
+        self._free = list(range(n_pages - 1, -1, -1))   # pop() takes page 0
+
+    # ---- host mirror ----
+    @property
+    def page(self) -> int:
+        return self._page
+
+    @property
+    def n_pages(self) -> int:
+        return self.k_pool.size(0)
+
+    @property
+    def free_pages(self) -> int:
+        return len(self._free)
+
+    @property
+    def capacity(self) -> int:
+        """Local positions one sequence can hold: the table's width."""
+        return self.page_table.size(1) * self._page
+
+    @property
+    def _row_bytes(self) -> int:
+        return self.k_pool.size(3) * self.k_pool.element_size()
+
+    def _reserve(self, ends: dict[int, int]) -> None:
+        """ends[b]: local positions row b is about to hold. Raise if the
+        pool cannot give every row its pages (nothing is taken then); else
+        take them and write their table entries."""
+        left = len(self._free)
+        for b, end in ends.items():
+            need = (end + self._page - 1) // self._page - len(self._pages[b])
+            if need > left:
+                raise RuntimeError(
+                    f"PagedDecodeSession pool exhausted: row {b} needs "
+                    f"{need} more page(s) of {self._page} tokens, {left} of "
+                    f"{self.n_pages} free (grow pool_tokens or reset a row)")
+            left -= max(need, 0)
+        for b, end in ends.items():
+            while len(self._pages[b]) * self._page < end:
+                pid = self._free.pop()
+                j = len(self._pages[b])
+                self._pages[b].append(pid)
+                self.page_table[b, j : j + 1].fill_(pid)
+
+    def _step_ends(self, mask: list[bool]) -> dict[int, int]:
+        """Capacity check of one append step, then the rows this rank
+        stores a token for -> the local positions they will hold."""
+        ends = {}
+        for b, on in enumerate(mask):
+            if not on:
+                continue
+            owner, pos = _place(self.totals[b], self.block, self.world)
+            if owner != self.rank:
+                continue
+            if pos >= self.capacity:
+                raise RuntimeError(
+                    f"PagedDecodeSession capacity exceeded: row {b} local "
+                    f"shard full at {self.local_lens[b]} tokens (grow "
+                    f"max_tokens)")
+            ends[b] = pos + 1
+        return ends
+
+    def _rows(self, b: int, n: int):
+        """Row b's first n local positions gathered from its pages into
+        contiguous (1, Hkv, n, D) K and V."""
+        idx = torch.tensor(self._pages[b][: (n + self._page - 1) // self._page],
+                           dtype=torch.long, device=self.device)
+        out = []
+        for pool in (self.k_pool, self.v_pool):
+            pages = pool.index_select(0, idx)          # (np, Hkv, page, D)
+            rows = pages.permute(1, 0, 2, 3).reshape(
+                1, pool.size(1), -1, pool.size(3))
+            out.append(rows[:, :, :n].contiguous())
+        return out
+
+    # ---- cache updates ----
+    def prefill(self, b: int, k_seq: torch.Tensor, v_seq: torch.Tensor) -> None:
+        """RaggedDecodeSession.prefill; the owned chunks are stored page by
+        page."""
+        if k_seq.dim() == 4:
+            k_seq, v_seq = k_seq[0], v_seq[0]
+        t_total = k_seq.shape[1]
+        chunks = []   # (source offset, n, local position) of the owned ones
+        total, t = self.totals[b], 0
+        while t < t_total:
+            n = min(self.block - total % self.block, t_total - t)
+            owner, pos = _place(total, self.block, self.world)
+            if owner == self.rank:
+                if pos + n > self.capacity:
+                    raise RuntimeError(
+                        f"PagedDecodeSession capacity exceeded during "
+                        f"prefill: row {b} at {pos}+{n} tokens (grow "
+                        f"max_tokens)")
+                chunks.append((t, n, pos))
+            total += n
+            t += n
+        if chunks:
+            self._reserve({b: max(pos + n for _, n, pos in chunks)})
+        for t, n, pos in chunks:
+            self.local_lens[b] = pos + n
+            while n > 0:
+                off = pos % self._page
+                m = min(n, self._page - off)
+                pid = self._pages[b][pos // self._page]
+                self.k_pool[pid, :, off : off + m] = \
+                    k_seq[:, t : t + m].to(self.k_pool.dtype)
+                self.v_pool[pid, :, off : off + m] = \
+                    v_seq[:, t : t + m].to(self.v_pool.dtype)
+                t, pos, n = t + m, pos + m, n - m
+        self.totals[b] = total
+        self._push_lengths(b)
+
+    def append(self, k_new: torch.Tensor, v_new: torch.Tensor,
+               active=None) -> None:
+        """RaggedDecodeSession.append; a row that lands on a new page gets
+        it before the launch."""
+        mask = self._mask(active)
+        ends = self._step_ends(mask)
+        self._reserve(ends)
+        if self._append_kernel_ok():
+            self._ext().kv_pool_append(
+                self.k_pool, self.v_pool, self.page_table,
+                k_new.to(self.k_pool.dtype).contiguous(),
+                v_new.to(self.v_pool.dtype).contiguous(), self.total_dev,
+                self.local_len_dev, self._mask_dev(mask), self.block,
+                self.rank, self.world)
+            self._advance(mask)
+            return
+        for b, end in ends.items():
+            pid, off = self._pages[b][(end - 1) // self._page], \
+                (end - 1) % self._page
+            self.k_pool[pid, :, off : off + 1] = k_new[b].to(self.k_pool.dtype)
+            self.v_pool[pid, :, off : off + 1] = v_new[b].to(self.v_pool.dtype)
+        self._advance(mask)
+        self.total_dev.copy_(torch.tensor(self.totals, dtype=torch.long))
+        self.local_len_dev.copy_(torch.tensor(self.local_lens,
+                                              dtype=torch.long))
+
+    def reset(self, b: int) -> None:
+        """Free slot b for a new sequence: its lengths go to 0 on host and
+        device and its pages back to the free list (the next ones handed
+        out); nothing is cleared."""
+        super().reset(b)
+        self._free.extend(reversed(self._pages[b]))
+        self._pages[b] = []
+
+    # ---- attention ----
+    def _paged_kernel_ok(self, q: torch.Tensor) -> bool:
+        # the predicate of _zero_copy_ok: it reads the cache's dtype and
+        # head_dim only, which the pool shares
+        return _zero_copy_ok(q, self.k_pool)
+
+    def _local_partial(self, q: torch.Tensor, softmax_scale: float | None):
+        if self._paged_kernel_ok(q):
+            scale = (softmax_scale if softmax_scale is not None
+                     else 1.0 / math.sqrt(q.shape[-1]))
+            return self._ext().flash_attention_paged(
+                q.contiguous(), self.k_pool, self.v_pool, self.page_table,
+                self.local_len_dev, scale)
+        outs, lses = [], []
+        for b, n in enumerate(self.local_lens):
+            qb = q[b : b + 1]
+            if n > 0:
+                k, v = self._rows(b, n)
+                if q.device.type == "cuda" and k.dtype == torch.float32:
+                    # the GPU kernels take no fp32 K/V: the gathered copy
+                    # goes in the query's dtype
+                    k, v = k.to(q.dtype), v.to(q.dtype)
+                o, l = local_attention(qb, k, v, softmax_scale)
+            else:
+                o, l = _empty_partial(qb)
+            outs.append(o)
+            lses.append(l)
+        return torch.cat(outs), torch.cat(lses)
+
+    def graphed_step(self, q_static: torch.Tensor, k_static: torch.Tensor,
+                     v_static: torch.Tensor,
+                     softmax_scale: float | None = None,
+                     combine: str = "auto"):
+        """RaggedDecodeSession.graphed_step over the pool: paged append,
+        paged attend and split combine captured as one linear chain.
+        ``replay(active)`` assigns the step's new pages eagerly before the
+        graph replays; the page table is a static buffer, so the replay sees
+        the new entries."""
+        if self.device.type != "cuda":
+            raise ValueError("graphed_step needs a GPU session")
+        # never capture the gathering path: it would freeze the capture-time
+        # lengths and pages into every replay
+        if not self._paged_kernel_ok(q_static):
+            raise ValueError(
+                "graphed_step: the paged cache kernel does not take this "
+                "session (needs head_dim 128, a bf16/fp16 query, a pool of "
+                "the query's dtype or fp8 under bf16, and Hq/Hkv <= 16)")
+        if not self._append_kernel_ok():
+            raise ValueError("graphed_step: the append kernel needs cache "
+                             "rows of a multiple of 4 bytes")
+        ext = self._ext()
+        active_dev = torch.zeros(self.batch, dtype=torch.uint8,
+                                 device=self.device)
+        scale = (softmax_scale if softmax_scale is not None
+                 else 1.0 / math.sqrt(q_static.shape[-1]))
+
+        def step():
+            ext.kv_pool_append(
+                self.k_pool, self.v_pool, self.page_table,
+                k_static.to(self.k_pool.dtype).contiguous(),
+                v_static.to(self.v_pool.dtype).contiguous(), self.total_dev,
+                self.local_len_dev, active_dev, self.block, self.rank,
+                self.world)
+            return ext.flash_attention_paged(
+                q_static.contiguous(), self.k_pool, self.v_pool,
+                self.page_table, self.local_len_dev, scale)
+
+        # warm-up on a side stream (allocator + kernels) under an all-zero
+        # mask, so no length moves; then capture
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                step()
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out_l, lse_l = step()
+        self._graph = graph  # keep alive
+        self._active_dev = active_dev
+
+        in_buffer = [[False] * self.batch]   # what active_dev holds now
+
+        def replay(active=None) -> torch.Tensor:
+            mask = self._mask(active)
+            self._reserve(self._step_ends(mask))
             self._advance(mask)
             if mask != in_buffer[0]:   # a steady mask costs no copy at all
                 active_dev.copy_(self._mask_dev(mask))
