@@ -39,6 +39,74 @@ _DTYPES = {
 }
 
 
+def _rank_world(group) -> tuple[int, int]:
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(group), dist.get_world_size(group)
+    return 0, 1
+
+
+def _local_cap(max_tokens: int, block: int, world: int) -> int:
+    """Positions max_tokens asks of one rank's shard: whole blocks, one
+    spare."""
+    blocks_total = (max_tokens + block - 1) // block + 1
+    return ((blocks_total + world - 1) // world) * block
+
+
+def _scale(softmax_scale: float | None, q: torch.Tensor) -> float:
+    return (softmax_scale if softmax_scale is not None
+            else 1.0 / math.sqrt(q.shape[-1]))
+
+
+def _place(t: int, block: int, world: int) -> tuple[int, int]:
+    """(owning rank, local position) of global token t: the block-cyclic
+    formula of the module docstring. kv_append_kernel (ops/hip) computes the
+    same two numbers on the device."""
+    blk = t // block
+    return blk % world, block * (blk // world) + t % block
+
+
+def _empty_partial(q: torch.Tensor):
+    """The partial of a shard that holds no key: out = 0, lse = -inf."""
+    b, hq, tq, d = q.shape
+    out_l = torch.zeros(b, hq, tq, d, dtype=torch.float32, device=q.device)
+    lse_l = torch.full((b, hq, tq), float("-inf"), dtype=torch.float32,
+                       device=q.device)
+    return out_l, lse_l
+
+
+def _zero_copy_ok(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """Whether the zero-copy cache kernels take q over the KV store k (a
+    cache slab or a page pool: only its dtype, head count and head_dim are
+    read). Mirrors the TORCH_CHECKs of bindings.cpp cache_decode: D=128; q
+    bf16/fp16; KV dtype == q dtype or fp8 KV under a bf16 q; (Hq/Hkv)*Tq <=
+    16 (MFMA-M batching)."""
+    return (
+        q.device.type == "cuda"
+        and k.size(3) == 128
+        and q.dtype in (torch.bfloat16, torch.float16)
+        and (
+            k.dtype == q.dtype
+            or (k.dtype == torch.float8_e4m3fn and q.dtype == torch.bfloat16)
+        )
+        and (q.shape[1] // k.shape[1]) * q.shape[2] <= 16
+    )
+
+
+def _capture(fn):
+    """Warm fn up on a side stream (allocator + kernels), then capture it
+    into a hipGraph -> (graph, what fn returned under capture)."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = fn()
+    return graph, out
+
+
 class DecodeSession:
     """Token-by-token decode over a sharded, growable KV cache."""
 
@@ -54,16 +122,11 @@ class DecodeSession:
         group: dist.ProcessGroup | None = None,
     ) -> None:
         self.device = torch.device(device)
-        if dist.is_available() and dist.is_initialized():
-            self.rank = dist.get_rank(group)
-            self.world = dist.get_world_size(group)
-        else:
-            self.rank, self.world = 0, 1
+        self.rank, self.world = _rank_world(group)
         self.group = group
         self.block = block
         self.mx = isinstance(kv_dtype, str) and kv_dtype in ("mx", "fp8_mx")
-        blocks_total = (max_tokens + block - 1) // block + 1
-        local_cap = ((blocks_total + self.world - 1) // self.world) * block
+        local_cap = _local_cap(max_tokens, block, self.world)
         if self.mx:
             # MX block-scaled fp8 cache (quant.py layout): e4m3 payload +
             # per-block E8M0 scales, quantized in closed 64-token WINDOWS
@@ -205,12 +268,7 @@ class DecodeSession:
                 parts.append(local_attention(q.float(), kt.float(),
                                              vt.float(), softmax_scale))
         if not parts:
-            b, hq, tq, d = q.shape
-            out_l = torch.zeros(b, hq, tq, d, dtype=torch.float32,
-                                device=q.device)
-            lse_l = torch.full((b, hq, tq), float("-inf"),
-                               dtype=torch.float32, device=q.device)
-            return out_l, lse_l
+            return _empty_partial(q)
         if len(parts) == 1:
             return parts[0]
         return combine_partials(torch.stack([p[0] for p in parts]),
@@ -219,23 +277,9 @@ class DecodeSession:
     def _local_partial(self, q: torch.Tensor, softmax_scale: float | None):
         if self.mx:
             return self._local_partial_mx(q, softmax_scale)
-        # zero-copy eligibility mirrors the binding's TORCH_CHECKs
-        # (bindings.cpp flash_attention_cache): D=128; q bf16/fp16; cache
-        # dtype == q dtype or fp8 cache under a bf16 q; (Hq/Hkv)*Tq <= 16
-        # (MFMA-M batching). Anything else falls through to the generic
-        # slice + local_attention path, which handles those cases.
-        zero_copy_ok = (
-            q.device.type == "cuda"
-            and self.k.size(3) == 128
-            and q.dtype in (torch.bfloat16, torch.float16)
-            and (
-                self.k.dtype == q.dtype
-                or (self.k.dtype == torch.float8_e4m3fn
-                    and q.dtype == torch.bfloat16)
-            )
-            and (q.shape[1] // self.k.shape[1]) * q.shape[2] <= 16
-        )
-        if zero_copy_ok:
+        # anything the zero-copy kernel does not take falls through to the
+        # generic slice + local_attention path, which handles those cases
+        if _zero_copy_ok(q, self.k):
             # zero-copy cache path: the kernel takes the cache's head stride
             # and reads the LIVE length from a device scalar, so this call
             # is hipGraph-capturable (graphed_attend) and never copies KV.
@@ -250,19 +294,14 @@ class DecodeSession:
                 if not hasattr(self, "_len_dev"):
                     self._len_dev = torch.zeros(1, dtype=torch.long,
                                                 device=self.device)
-                scale = (softmax_scale if softmax_scale is not None
-                         else 1.0 / math.sqrt(q.shape[-1]))
-                return ext.flash_attention_cache(q.contiguous(), self.k,
-                                                 self.v, self._len_dev, scale)
+                return ext.flash_attention_cache(
+                    q.contiguous(), self.k, self.v, self._len_dev,
+                    _scale(softmax_scale, q))
         if self.local_len > 0:
             k = self.k[:, :, : self.local_len].contiguous()
             v = self.v[:, :, : self.local_len].contiguous()
             return local_attention(q, k, v, softmax_scale)
-        b, hq, tq, d = q.shape
-        out_l = torch.zeros(b, hq, tq, d, dtype=torch.float32, device=q.device)
-        lse_l = torch.full((b, hq, tq), float("-inf"), dtype=torch.float32,
-                           device=q.device)
-        return out_l, lse_l
+        return _empty_partial(q)
 
     def attend(self, q: torch.Tensor, softmax_scale: float | None = None,
                combine: str = "auto") -> torch.Tensor:
@@ -304,16 +343,8 @@ class DecodeSession:
                 "python merge with per-call allocations; use eager "
                 "attend() (the MX decode kernel itself is ~0.2 ms at "
                 "128K — not launch-bound)")
-        # warmup on a side stream (allocator + kernels), then capture
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._local_partial(q_static, softmax_scale)
-        torch.cuda.current_stream().wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out_l, lse_l = self._local_partial(q_static, softmax_scale)
+        graph, (out_l, lse_l) = _capture(
+            lambda: self._local_partial(q_static, softmax_scale))
         self._graph = graph  # keep alive
 
         if self.world == 1:
@@ -368,39 +399,6 @@ class DecodeSession:
 # --------------------------------------------------------------------------
 # ragged batch: one length per sequence
 # --------------------------------------------------------------------------
-def _place(t: int, block: int, world: int) -> tuple[int, int]:
-    """(owning rank, local position) of global token t: the block-cyclic
-    formula of the module docstring. kv_append_kernel (ops/hip) computes the
-    same two numbers on the device."""
-    blk = t // block
-    return blk % world, block * (blk // world) + t % block
-
-
-def _empty_partial(q: torch.Tensor):
-    """The partial of a shard that holds no key: out = 0, lse = -inf."""
-    b, hq, tq, d = q.shape
-    out_l = torch.zeros(b, hq, tq, d, dtype=torch.float32, device=q.device)
-    lse_l = torch.full((b, hq, tq), float("-inf"), dtype=torch.float32,
-                       device=q.device)
-    return out_l, lse_l
-
-
-def _zero_copy_ok(q: torch.Tensor, k: torch.Tensor) -> bool:
-    """The predicate of DecodeSession._local_partial (it mirrors the
-    TORCH_CHECKs of bindings.cpp flash_attention_cache): D=128; q bf16/fp16;
-    cache dtype == q dtype or fp8 cache under a bf16 q; (Hq/Hkv)*Tq <= 16."""
-    return (
-        q.device.type == "cuda"
-        and k.size(3) == 128
-        and q.dtype in (torch.bfloat16, torch.float16)
-        and (
-            k.dtype == q.dtype
-            or (k.dtype == torch.float8_e4m3fn and q.dtype == torch.bfloat16)
-        )
-        and (q.shape[1] // k.shape[1]) * q.shape[2] <= 16
-    )
-
-
 class RaggedDecodeSession:
     """Token-by-token decode of a BATCH whose sequences have their own
     lengths, over the same block-cyclic sharded cache as DecodeSession.
@@ -415,6 +413,9 @@ class RaggedDecodeSession:
 
     ``max_tokens`` is per sequence. Tq = 1; no MX cache (its 64-token
     quantization windows are host-side state per sequence).
+
+    Where a local position lives is the subclass seam: the methods under
+    "storage" below are all that PagedDecodeSession replaces.
     """
 
     def __init__(
@@ -448,16 +449,10 @@ class RaggedDecodeSession:
             raise ValueError(f"{name}: unknown kv_dtype "
                              f"{kv_dtype!r}")
         self.device = torch.device(device)
-        if dist.is_available() and dist.is_initialized():
-            self.rank = dist.get_rank(group)
-            self.world = dist.get_world_size(group)
-        else:
-            self.rank, self.world = 0, 1
+        self.rank, self.world = _rank_world(group)
         self.group = group
         self.block = block
         self.batch = batch
-        blocks_total = (max_tokens + block - 1) // block + 1
-        local_cap = ((blocks_total + self.world - 1) // self.world) * block
         td = _DTYPES[kv_dtype] if isinstance(kv_dtype, str) else kv_dtype
         self.total_dev = torch.zeros(batch, dtype=torch.long,
                                      device=self.device)
@@ -465,17 +460,62 @@ class RaggedDecodeSession:
         self.totals = [0] * batch       # global tokens of each sequence
         self.local_lens = [0] * batch   # of them, in THIS rank's shard
         self._mask_cache: dict[tuple, torch.Tensor] = {}
-        return td, local_cap
+        return td, _local_cap(max_tokens, block, self.world)
 
-    # ---- host mirror ----
+    # ---- storage: a (B, Hkv, capacity, D) slab ----
+    _graph_refusal = (
+        "graphed_step: the zero-copy cache kernel does not take this "
+        "session (needs head_dim 128, a bf16/fp16 query, a cache of "
+        "the query's dtype or fp8 under bf16, and Hq/Hkv <= 16)")
+
+    @property
+    def _kv(self) -> torch.Tensor:
+        """The K storage: its dtype, head count and head_dim are the
+        session's."""
+        return self.k
+
     @property
     def capacity(self) -> int:
         return self.k.size(2)
 
-    @property
-    def _row_bytes(self) -> int:
-        return self.k.size(3) * self.k.element_size()
+    def _reserve(self, ends: dict[int, int]) -> None:
+        """ends[b]: local positions row b is about to hold. The slab holds
+        every position up to capacity already."""
 
+    def _store(self, b: int, pos: int, k_rows: torch.Tensor,
+               v_rows: torch.Tensor) -> None:
+        """Host store of (Hkv, n, D) rows of sequence b at local positions
+        [pos, pos + n), cast to the storage dtype."""
+        n = k_rows.shape[1]
+        self.k[b, :, pos : pos + n] = k_rows.to(self.k.dtype)
+        self.v[b, :, pos : pos + n] = v_rows.to(self.v.dtype)
+
+    def _rows(self, b: int, n: int):
+        """Row b's first n local positions as contiguous (1, Hkv, n, D) K
+        and V."""
+        return (self.k[b : b + 1, :, :n].contiguous(),
+                self.v[b : b + 1, :, :n].contiguous())
+
+    def _fallback_rows(self, q: torch.Tensor, b: int, n: int):
+        """_rows as local_attention takes them under query q."""
+        return self._rows(b, n)
+
+    def _launch_append(self, ext, k_new, v_new, active_dev) -> None:
+        # the cast to the cache dtype (fp8 included) stays a torch op; the
+        # kernel copies bytes
+        ext.kv_cache_append(
+            self.k, self.v, k_new.to(self.k.dtype).contiguous(),
+            v_new.to(self.v.dtype).contiguous(), self.total_dev,
+            self.local_len_dev, active_dev, self.block, self.rank,
+            self.world)
+
+    def _launch_attend(self, ext, q, scale: float):
+        # one launch for the whole ragged batch: every block clips its
+        # chunk to its own row's length, read from local_len_dev
+        return ext.flash_attention_cache(q.contiguous(), self.k, self.v,
+                                         self.local_len_dev, scale)
+
+    # ---- host mirror ----
     def _mask(self, active) -> list[bool]:
         if active is None:
             return [True] * self.batch
@@ -501,17 +541,24 @@ class RaggedDecodeSession:
             self._mask_cache[key] = dev
         return dev
 
-    def _check_capacity(self, mask: list[bool]) -> None:
-        """Raise before anything is launched or stored, naming the row."""
+    def _step_ends(self, mask: list[bool]) -> dict[int, int]:
+        """Capacity check of one append step, naming the row, before
+        anything is reserved, launched or stored; then the rows this rank
+        stores a token for -> the local positions they will hold."""
+        ends, cap = {}, self.capacity
         for b, on in enumerate(mask):
             if not on:
                 continue
             owner, pos = _place(self.totals[b], self.block, self.world)
-            if owner == self.rank and pos >= self.capacity:
+            if owner != self.rank:
+                continue
+            if pos >= cap:
                 raise RuntimeError(
-                    f"RaggedDecodeSession capacity exceeded: row {b} local "
+                    f"{type(self).__name__} capacity exceeded: row {b} local "
                     f"shard full at {self.local_lens[b]} tokens (grow "
                     f"max_tokens)")
+            ends[b] = pos + 1
+        return ends
 
     def _advance(self, mask: list[bool]) -> None:
         for b, on in enumerate(mask):
@@ -527,7 +574,8 @@ class RaggedDecodeSession:
         self.local_len_dev[b : b + 1].fill_(self.local_lens[b])
 
     def _append_kernel_ok(self) -> bool:
-        return self.device.type == "cuda" and self._row_bytes % 4 == 0
+        row_bytes = self._kv.size(3) * self._kv.element_size()
+        return self.device.type == "cuda" and row_bytes % 4 == 0
 
     @classmethod
     def _ext(cls):
@@ -556,15 +604,16 @@ class RaggedDecodeSession:
             if owner == self.rank:
                 if pos + n > self.capacity:
                     raise RuntimeError(
-                        f"RaggedDecodeSession capacity exceeded during "
+                        f"{type(self).__name__} capacity exceeded during "
                         f"prefill: row {b} at {pos}+{n} tokens (grow "
                         f"max_tokens)")
                 chunks.append((t, n, pos))
             total += n
             t += n
+        if chunks:
+            self._reserve({b: max(pos + n for _, n, pos in chunks)})
         for t, n, pos in chunks:
-            self.k[b, :, pos : pos + n] = k_seq[:, t : t + n].to(self.k.dtype)
-            self.v[b, :, pos : pos + n] = v_seq[:, t : t + n].to(self.v.dtype)
+            self._store(b, pos, k_seq[:, t : t + n], v_seq[:, t : t + n])
             self.local_lens[b] = pos + n
         self.totals[b] = total
         self._push_lengths(b)
@@ -576,24 +625,15 @@ class RaggedDecodeSession:
         rank calls this with the same arguments; only a token's owning rank
         stores it."""
         mask = self._mask(active)
-        self._check_capacity(mask)
+        ends = self._step_ends(mask)
+        self._reserve(ends)
         if self._append_kernel_ok():
-            # the cast to the cache dtype (fp8 included) stays a torch op;
-            # the kernel copies bytes
-            self._ext().kv_cache_append(
-                self.k, self.v, k_new.to(self.k.dtype).contiguous(),
-                v_new.to(self.v.dtype).contiguous(), self.total_dev,
-                self.local_len_dev, self._mask_dev(mask), self.block,
-                self.rank, self.world)
+            self._launch_append(self._ext(), k_new, v_new,
+                                self._mask_dev(mask))
             self._advance(mask)
             return
-        for b, on in enumerate(mask):
-            if not on:
-                continue
-            owner, pos = _place(self.totals[b], self.block, self.world)
-            if owner == self.rank:
-                self.k[b, :, pos : pos + 1] = k_new[b].to(self.k.dtype)
-                self.v[b, :, pos : pos + 1] = v_new[b].to(self.v.dtype)
+        for b, end in ends.items():
+            self._store(b, end - 1, k_new[b], v_new[b])
         self._advance(mask)
         self.total_dev.copy_(torch.tensor(self.totals, dtype=torch.long))
         self.local_len_dev.copy_(torch.tensor(self.local_lens,
@@ -608,20 +648,15 @@ class RaggedDecodeSession:
 
     # ---- attention ----
     def _local_partial(self, q: torch.Tensor, softmax_scale: float | None):
-        if _zero_copy_ok(q, self.k):
-            # one launch for the whole ragged batch: every block clips its
-            # chunk to its own row's length, read from local_len_dev
-            scale = (softmax_scale if softmax_scale is not None
-                     else 1.0 / math.sqrt(q.shape[-1]))
-            return self._ext().flash_attention_cache(
-                q.contiguous(), self.k, self.v, self.local_len_dev, scale)
+        if _zero_copy_ok(q, self._kv):
+            return self._launch_attend(self._ext(), q,
+                                       _scale(softmax_scale, q))
         outs, lses = [], []
         for b, n in enumerate(self.local_lens):
             qb = q[b : b + 1]
             if n > 0:
-                o, l = local_attention(qb, self.k[b : b + 1, :, :n].contiguous(),
-                                       self.v[b : b + 1, :, :n].contiguous(),
-                                       softmax_scale)
+                k, v = self._fallback_rows(qb, b, n)
+                o, l = local_attention(qb, k, v, softmax_scale)
             else:
                 o, l = _empty_partial(qb)
             outs.append(o)
@@ -646,50 +681,34 @@ class RaggedDecodeSession:
 
         Write the step's query and new K/V (B, Hkv, 1, D) into the static
         tensors, then ``replay(active=None)`` checks capacity on the host
-        mirror, advances it, copies the mask into the static device buffer
-        the capture reads, replays, and returns the output: the static
-        buffer at world size 1; at world size > 1 the local partial replays
-        from the graph and the collective runs eagerly (graphed_attend).
+        mirror, reserves what the step will hold (a paged session assigns
+        its new pages here, eagerly: the page table is a static buffer, so
+        the replay sees the new entries), advances the mirror, copies the
+        mask into the static device buffer the capture reads, replays, and
+        returns the output: the static buffer at world size 1; at world
+        size > 1 the local partial replays from the graph and the collective
+        runs eagerly (graphed_attend).
         """
         if self.device.type != "cuda":
             raise ValueError("graphed_step needs a GPU session")
-        # never capture the slicing path: it would freeze the capture-time
-        # lengths into every replay
-        if not _zero_copy_ok(q_static, self.k):
-            raise ValueError(
-                "graphed_step: the zero-copy cache kernel does not take this "
-                "session (needs head_dim 128, a bf16/fp16 query, a cache of "
-                "the query's dtype or fp8 under bf16, and Hq/Hkv <= 16)")
+        # never capture the per-row fallback: it would freeze the
+        # capture-time lengths (and pages) into every replay
+        if not _zero_copy_ok(q_static, self._kv):
+            raise ValueError(self._graph_refusal)
         if not self._append_kernel_ok():
             raise ValueError("graphed_step: the append kernel needs cache "
                              "rows of a multiple of 4 bytes")
         ext = self._ext()
         active_dev = torch.zeros(self.batch, dtype=torch.uint8,
                                  device=self.device)
-        scale = (softmax_scale if softmax_scale is not None
-                 else 1.0 / math.sqrt(q_static.shape[-1]))
+        scale = _scale(softmax_scale, q_static)
 
         def step():
-            ext.kv_cache_append(
-                self.k, self.v, k_static.to(self.k.dtype).contiguous(),
-                v_static.to(self.v.dtype).contiguous(), self.total_dev,
-                self.local_len_dev, active_dev, self.block, self.rank,
-                self.world)
-            return ext.flash_attention_cache(
-                q_static.contiguous(), self.k, self.v, self.local_len_dev,
-                scale)
+            self._launch_append(ext, k_static, v_static, active_dev)
+            return self._launch_attend(ext, q_static, scale)
 
-        # warm-up on a side stream (allocator + kernels) under an all-zero
-        # mask, so no length moves; then capture
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                step()
-        torch.cuda.current_stream().wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out_l, lse_l = step()
+        # the warm-up runs under the all-zero mask, so no length moves
+        graph, (out_l, lse_l) = _capture(step)
         self._graph = graph  # keep alive
         self._active_dev = active_dev
 
@@ -697,7 +716,7 @@ class RaggedDecodeSession:
 
         def replay(active=None) -> torch.Tensor:
             mask = self._mask(active)
-            self._check_capacity(mask)
+            self._reserve(self._step_ends(mask))
             self._advance(mask)
             if mask != in_buffer[0]:   # a steady mask costs no copy at all
                 active_dev.copy_(self._mask_dev(mask))
@@ -769,7 +788,6 @@ class PagedDecodeSession(RaggedDecodeSession):
         self._pages: list[list[int]] = [[] for _ in range(batch)]
         self._free = list(range(n_pages - 1, -1, -1))   # pop() takes page 0
 
-    # ---- host mirror ----
     @property
     def page(self) -> int:
         return self._page
@@ -782,19 +800,24 @@ class PagedDecodeSession(RaggedDecodeSession):
     def free_pages(self) -> int:
         return len(self._free)
 
+    # ---- storage: (n_pages, Hkv, page, D) pools behind the page table ----
+    _graph_refusal = (
+        "graphed_step: the paged cache kernel does not take this "
+        "session (needs head_dim 128, a bf16/fp16 query, a pool of "
+        "the query's dtype or fp8 under bf16, and Hq/Hkv <= 16)")
+
+    @property
+    def _kv(self) -> torch.Tensor:
+        return self.k_pool
+
     @property
     def capacity(self) -> int:
         """Local positions one sequence can hold: the table's width."""
         return self.page_table.size(1) * self._page
 
-    @property
-    def _row_bytes(self) -> int:
-        return self.k_pool.size(3) * self.k_pool.element_size()
-
     def _reserve(self, ends: dict[int, int]) -> None:
-        """ends[b]: local positions row b is about to hold. Raise if the
-        pool cannot give every row its pages (nothing is taken then); else
-        take them and write their table entries."""
+        """Raise if the pool cannot give every row its pages (nothing is
+        taken then); else take them and write their table entries."""
         left = len(self._free)
         for b, end in ends.items():
             need = (end + self._page - 1) // self._page - len(self._pages[b])
@@ -811,23 +834,19 @@ class PagedDecodeSession(RaggedDecodeSession):
                 self._pages[b].append(pid)
                 self.page_table[b, j : j + 1].fill_(pid)
 
-    def _step_ends(self, mask: list[bool]) -> dict[int, int]:
-        """Capacity check of one append step, then the rows this rank
-        stores a token for -> the local positions they will hold."""
-        ends = {}
-        for b, on in enumerate(mask):
-            if not on:
-                continue
-            owner, pos = _place(self.totals[b], self.block, self.world)
-            if owner != self.rank:
-                continue
-            if pos >= self.capacity:
-                raise RuntimeError(
-                    f"PagedDecodeSession capacity exceeded: row {b} local "
-                    f"shard full at {self.local_lens[b]} tokens (grow "
-                    f"max_tokens)")
-            ends[b] = pos + 1
-        return ends
+    def _store(self, b: int, pos: int, k_rows: torch.Tensor,
+               v_rows: torch.Tensor) -> None:
+        # page by page; _reserve has assigned every page touched
+        t, n = 0, k_rows.shape[1]
+        while t < n:
+            off = pos % self._page
+            m = min(n - t, self._page - off)
+            pid = self._pages[b][pos // self._page]
+            self.k_pool[pid, :, off : off + m] = \
+                k_rows[:, t : t + m].to(self.k_pool.dtype)
+            self.v_pool[pid, :, off : off + m] = \
+                v_rows[:, t : t + m].to(self.v_pool.dtype)
+            t, pos = t + m, pos + m
 
     def _rows(self, b: int, n: int):
         """Row b's first n local positions gathered from its pages into
@@ -842,68 +861,26 @@ class PagedDecodeSession(RaggedDecodeSession):
             out.append(rows[:, :, :n].contiguous())
         return out
 
-    # ---- cache updates ----
-    def prefill(self, b: int, k_seq: torch.Tensor, v_seq: torch.Tensor) -> None:
-        """RaggedDecodeSession.prefill; the owned chunks are stored page by
-        page."""
-        if k_seq.dim() == 4:
-            k_seq, v_seq = k_seq[0], v_seq[0]
-        t_total = k_seq.shape[1]
-        chunks = []   # (source offset, n, local position) of the owned ones
-        total, t = self.totals[b], 0
-        while t < t_total:
-            n = min(self.block - total % self.block, t_total - t)
-            owner, pos = _place(total, self.block, self.world)
-            if owner == self.rank:
-                if pos + n > self.capacity:
-                    raise RuntimeError(
-                        f"PagedDecodeSession capacity exceeded during "
-                        f"prefill: row {b} at {pos}+{n} tokens (grow "
-                        f"max_tokens)")
-                chunks.append((t, n, pos))
-            total += n
-            t += n
-        if chunks:
-            self._reserve({b: max(pos + n for _, n, pos in chunks)})
-        for t, n, pos in chunks:
-            self.local_lens[b] = pos + n
-            while n > 0:
-                off = pos % self._page
-                m = min(n, self._page - off)
-                pid = self._pages[b][pos // self._page]
-                self.k_pool[pid, :, off : off + m] = \
-                    k_seq[:, t : t + m].to(self.k_pool.dtype)
-                self.v_pool[pid, :, off : off + m] = \
-                    v_seq[:, t : t + m].to(self.v_pool.dtype)
-                t, pos, n = t + m, pos + m, n - m
-        self.totals[b] = total
-        self._push_lengths(b)
+    def _fallback_rows(self, q: torch.Tensor, b: int, n: int):
+        k, v = self._rows(b, n)
+        if q.device.type == "cuda" and k.dtype == torch.float32:
+            # the GPU kernels take no fp32 K/V: the gathered copy goes in
+            # the query's dtype
+            k, v = k.to(q.dtype), v.to(q.dtype)
+        return k, v
 
-    def append(self, k_new: torch.Tensor, v_new: torch.Tensor,
-               active=None) -> None:
-        """RaggedDecodeSession.append; a row that lands on a new page gets
-        it before the launch."""
-        mask = self._mask(active)
-        ends = self._step_ends(mask)
-        self._reserve(ends)
-        if self._append_kernel_ok():
-            self._ext().kv_pool_append(
-                self.k_pool, self.v_pool, self.page_table,
-                k_new.to(self.k_pool.dtype).contiguous(),
-                v_new.to(self.v_pool.dtype).contiguous(), self.total_dev,
-                self.local_len_dev, self._mask_dev(mask), self.block,
-                self.rank, self.world)
-            self._advance(mask)
-            return
-        for b, end in ends.items():
-            pid, off = self._pages[b][(end - 1) // self._page], \
-                (end - 1) % self._page
-            self.k_pool[pid, :, off : off + 1] = k_new[b].to(self.k_pool.dtype)
-            self.v_pool[pid, :, off : off + 1] = v_new[b].to(self.v_pool.dtype)
-        self._advance(mask)
-        self.total_dev.copy_(torch.tensor(self.totals, dtype=torch.long))
-        self.local_len_dev.copy_(torch.tensor(self.local_lens,
-                                              dtype=torch.long))
+    def _launch_append(self, ext, k_new, v_new, active_dev) -> None:
+        ext.kv_pool_append(
+            self.k_pool, self.v_pool, self.page_table,
+            k_new.to(self.k_pool.dtype).contiguous(),
+            v_new.to(self.v_pool.dtype).contiguous(), self.total_dev,
+            self.local_len_dev, active_dev, self.block, self.rank,
+            self.world)
+
+    def _launch_attend(self, ext, q, scale: float):
+        return ext.flash_attention_paged(
+            q.contiguous(), self.k_pool, self.v_pool, self.page_table,
+            self.local_len_dev, scale)
 
     def reset(self, b: int) -> None:
         """Free slot b for a new sequence: its lengths go to 0 on host and
@@ -912,102 +889,3 @@ class PagedDecodeSession(RaggedDecodeSession):
         super().reset(b)
         self._free.extend(reversed(self._pages[b]))
         self._pages[b] = []
-
-    # ---- attention ----
-    def _paged_kernel_ok(self, q: torch.Tensor) -> bool:
-        # the predicate of _zero_copy_ok: it reads the cache's dtype and
-        # head_dim only, which the pool shares
-        return _zero_copy_ok(q, self.k_pool)
-
-    def _local_partial(self, q: torch.Tensor, softmax_scale: float | None):
-        if self._paged_kernel_ok(q):
-            scale = (softmax_scale if softmax_scale is not None
-                     else 1.0 / math.sqrt(q.shape[-1]))
-            return self._ext().flash_attention_paged(
-                q.contiguous(), self.k_pool, self.v_pool, self.page_table,
-                self.local_len_dev, scale)
-        outs, lses = [], []
-        for b, n in enumerate(self.local_lens):
-            qb = q[b : b + 1]
-            if n > 0:
-                k, v = self._rows(b, n)
-                if q.device.type == "cuda" and k.dtype == torch.float32:
-                    # the GPU kernels take no fp32 K/V: the gathered copy
-                    # goes in the query's dtype
-                    k, v = k.to(q.dtype), v.to(q.dtype)
-                o, l = local_attention(qb, k, v, softmax_scale)
-            else:
-                o, l = _empty_partial(qb)
-            outs.append(o)
-            lses.append(l)
-        return torch.cat(outs), torch.cat(lses)
-
-    def graphed_step(self, q_static: torch.Tensor, k_static: torch.Tensor,
-                     v_static: torch.Tensor,
-                     softmax_scale: float | None = None,
-                     combine: str = "auto"):
-        """RaggedDecodeSession.graphed_step over the pool: paged append,
-        paged attend and split combine captured as one linear chain.
-        ``replay(active)`` assigns the step's new pages eagerly before the
-        graph replays; the page table is a static buffer, so the replay sees
-        the new entries."""
-        if self.device.type != "cuda":
-            raise ValueError("graphed_step needs a GPU session")
-        # never capture the gathering path: it would freeze the capture-time
-        # lengths and pages into every replay
-        if not self._paged_kernel_ok(q_static):
-            raise ValueError(
-                "graphed_step: the paged cache kernel does not take this "
-                "session (needs head_dim 128, a bf16/fp16 query, a pool of "
-                "the query's dtype or fp8 under bf16, and Hq/Hkv <= 16)")
-        if not self._append_kernel_ok():
-            raise ValueError("graphed_step: the append kernel needs cache "
-                             "rows of a multiple of 4 bytes")
-        ext = self._ext()
-        active_dev = torch.zeros(self.batch, dtype=torch.uint8,
-                                 device=self.device)
-        scale = (softmax_scale if softmax_scale is not None
-                 else 1.0 / math.sqrt(q_static.shape[-1]))
-
-        def step():
-            ext.kv_pool_append(
-                self.k_pool, self.v_pool, self.page_table,
-                k_static.to(self.k_pool.dtype).contiguous(),
-                v_static.to(self.v_pool.dtype).contiguous(), self.total_dev,
-                self.local_len_dev, active_dev, self.block, self.rank,
-                self.world)
-            return ext.flash_attention_paged(
-                q_static.contiguous(), self.k_pool, self.v_pool,
-                self.page_table, self.local_len_dev, scale)
-
-        # warm-up on a side stream (allocator + kernels) under an all-zero
-        # mask, so no length moves; then capture
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                step()
-        torch.cuda.current_stream().wait_stream(s)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out_l, lse_l = step()
-        self._graph = graph  # keep alive
-        self._active_dev = active_dev
-
-        in_buffer = [[False] * self.batch]   # what active_dev holds now
-
-        def replay(active=None) -> torch.Tensor:
-            mask = self._mask(active)
-            self._reserve(self._step_ends(mask))
-            self._advance(mask)
-            if mask != in_buffer[0]:   # a steady mask costs no copy at all
-                active_dev.copy_(self._mask_dev(mask))
-                in_buffer[0] = mask
-            graph.replay()
-            if self.world == 1:
-                return out_l
-            out, _ = tree_combine(out_l, lse_l, strategy=combine,
-                                  group=self.group)
-            return out
-
-        return replay
