@@ -473,16 +473,15 @@ def test_combine_rescale_finish_kernels(ext):
 
 
 @pytest.mark.parametrize("flag,val", [
-    ("TREE_ATTN_PREFILL4", "1"), ("TREE_ATTN_PREFILL5", "1"),
-    ("TREE_ATTN_PREFILL6", "1"), ("TREE_ATTN_PREFILL6", "2"),
-    ("TREE_ATTN_PREFILL6", "7"),
+    ("TREE_ATTN_PREFILL6", "7"), ("TREE_ATTN_PREFILL6", "0"),
 ])
-def test_experimental_prefill_variants(ext, flag, val):
-    """fa_prefill4/5/6 (env-gated variants) must stay numerically honest:
-    run in a subprocess because the route flag is latched at first call.
-    The shape list exercises gen6's asm interior loop (full 128-key tiles
-    below the causal frontier), the C boundary path (frontier, tails,
-    ragged rows) and the hand-off between them, plus GQA head mapping."""
+def test_env_selected_prefill_routes(ext, flag, val):
+    """The env-selected routes (gen7 named explicitly, and the fa_prefill2
+    fallback) must stay numerically honest: run in a subprocess because the
+    route flag is latched at first call. The shape list exercises gen7's asm
+    interior loop (full 128-key tiles below the causal frontier), the C
+    boundary path (frontier, tails, ragged rows) and the hand-off between
+    them, plus GQA head mapping."""
     import os
     import subprocess
     import sys
@@ -517,6 +516,36 @@ def test_experimental_prefill_variants(ext, flag, val):
     r = subprocess.run([sys.executable, "-c", code], capture_output=True,
                        text=True, env=env, timeout=300)
     assert r.returncode == 0 and "VARIANT_OK" in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.parametrize("val", ["2", "9"])
+def test_retired_prefill_route_refused(ext, val):
+    """A TREE_ATTN_PREFILL6 value that named a retired kernel is refused at
+    the first prefill call, never mapped to another kernel. Fresh child per
+    value (the route is latched); the shape is the smallest that takes the
+    prefill route (the decode route ends at G*Tq <= 16). Nothing launches."""
+    import os
+    import subprocess
+    import sys
+
+    code = (
+        "import torch\n"
+        "from tree_attention_torch_amd.ops import flash\n"
+        "ext = flash._load_extension()\n"
+        "q = torch.randn(1, 1, 17, 128, device='cuda').bfloat16()\n"
+        "try:\n"
+        "    ext.flash_attention(q, q.clone(), q.clone(), 128 ** -0.5, False, 0, 0)\n"
+        "except RuntimeError as e:\n"
+        "    assert 'TREE_ATTN_PREFILL6' in str(e), str(e)\n"
+        "    print('REFUSED_OK')\n"
+    )
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, TREE_ATTN_PREFILL6=val)
+    env["PYTHONPATH"] = os.pathsep.join(
+        p for p in (repo, os.environ.get("PYTHONPATH")) if p)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True,
+                       text=True, env=env, timeout=300)
+    assert r.returncode == 0 and "REFUSED_OK" in r.stdout, r.stdout + r.stderr
 
 
 def test_probe_gen6_qkt_stream(ext):
@@ -563,7 +592,8 @@ def test_fp8_narrow_head_padding(ext):
 
 def test_probe_gen6_softmax_stream(ext):
     """Generated softmax+pack asm stream: BIT-exact vs the proven C form
-    (fa_prefill5's softmax_pack + pswap) on identical inputs."""
+    (gen7's boundary-tile softmax + permlane32_redistribute) on identical
+    inputs."""
     torch.manual_seed(2)
     s_in = (torch.randn(64, 16) * 3).float().cuda()
     ml = torch.stack([torch.randn(64) * 2 - 1, torch.rand(64) * 5 + 0.1],

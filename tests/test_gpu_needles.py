@@ -136,18 +136,14 @@ def test_needle_cache_graph_replay(ext):
 
 
 @pytest.mark.parametrize("flag,val", [
-    ("TREE_ATTN_PREFILL4", "1"), ("TREE_ATTN_PREFILL5", "1"),
-    ("TREE_ATTN_PREFILL6", "1"), ("TREE_ATTN_PREFILL6", "2"),
     ("TREE_ATTN_PREFILL6", "7"), ("TREE_ATTN_PREFILL6", "0"),
-    ("TREE_ATTN_PREFILL_V1", "1"), ("TREE_ATTN_PREFILL6", "9"),
 ])
 def test_needle_prefill_env_variants(ext, flag, val):
     """The env-latched bf16 prefill kernels on the prefill rows of the table
     (every family, plain and guarded). The route flag is latched at first
     call, so each flag gets a fresh child process with its own timeout.
-    TREE_ATTN_PREFILL6=0 is the fallback fa_prefill2_kernel and
-    TREE_ATTN_PREFILL_V1 the first prefill kernel. TREE_ATTN_PREFILL6=9 is
-    an alias of 7: the element type comes from q's dtype, never the flag."""
+    TREE_ATTN_PREFILL6=7 names the default fa_prefill7_kernel and
+    TREE_ATTN_PREFILL6=0 is the fallback fa_prefill2_kernel."""
     tests_dir = os.path.dirname(os.path.abspath(__file__))
     repo = os.path.dirname(tests_dir)
     code = (f"import sys; sys.path.insert(0, {tests_dir!r}); "

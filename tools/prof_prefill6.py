@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Minimal driver for rocprofv3 counter capture on the prefill kernels.
 
-Env: TREE_ATTN_PREFILL6=1|2 (or unset for prefill2). Args: tq tkv causal
+Env: TREE_ATTN_PREFILL6=0 for prefill2 (unset or 7: gen7). Args: tq tkv causal
 iters (defaults 4096 4096 0 3).
 """
 import sys
