@@ -65,6 +65,17 @@ def _place(t: int, block: int, world: int) -> tuple[int, int]:
     return blk % world, block * (blk // world) + t % block
 
 
+def _n_local(t: int, block: int, rank: int, world: int) -> int:
+    """How many of the first t global tokens of a sequence `rank` owns: the
+    count _place implies, and local_len after t contiguous appends. A shard's
+    local positions are ordered by global position, so "sees global
+    positions < t" is "sees the local prefix of length _n_local(t)"
+    (kv_append_n_kernel computes the same number on the device)."""
+    full = t // block
+    return (block * ((full + world - 1 - rank) // world)
+            + (t % block if full % world == rank else 0))
+
+
 def _empty_partial(q: torch.Tensor):
     """The partial of a shard that holds no key: out = 0, lse = -inf."""
     b, hq, tq, d = q.shape
@@ -74,12 +85,15 @@ def _empty_partial(q: torch.Tensor):
     return out_l, lse_l
 
 
-def _zero_copy_ok(q: torch.Tensor, k: torch.Tensor) -> bool:
+def _zero_copy_ok(q: torch.Tensor, k: torch.Tensor,
+                  any_tq: bool = False) -> bool:
     """Whether the zero-copy cache kernels take q over the KV store k (a
     cache slab or a page pool: only its dtype, head count and head_dim are
     read). Mirrors the TORCH_CHECKs of bindings.cpp cache_decode: D=128; q
     bf16/fp16; KV dtype == q dtype or fp8 KV under a bf16 q; (Hq/Hkv)*Tq <=
-    16 (MFMA-M batching)."""
+    16 (MFMA-M batching). any_tq: the visible-length bindings
+    (cache_decode_qlen) loop over groups of query positions, so only Hq/Hkv
+    <= 16 is asked."""
     return (
         q.device.type == "cuda"
         and k.size(3) == 128
@@ -88,7 +102,7 @@ def _zero_copy_ok(q: torch.Tensor, k: torch.Tensor) -> bool:
             k.dtype == q.dtype
             or (k.dtype == torch.float8_e4m3fn and q.dtype == torch.bfloat16)
         )
-        and (q.shape[1] // k.shape[1]) * q.shape[2] <= 16
+        and (q.shape[1] // k.shape[1]) * (1 if any_tq else q.shape[2]) <= 16
     )
 
 
@@ -411,8 +425,11 @@ class RaggedDecodeSession:
     by the same formula. The host decides which rows are active, so the
     mirror is always exact, and capacity is checked on it before any launch.
 
-    ``max_tokens`` is per sequence. Tq = 1; no MX cache (its 64-token
-    quantization windows are host-side state per sequence).
+    ``max_tokens`` is per sequence. attend() takes one query row per
+    sequence; a speculative verify step takes up to 16 draft tokens per
+    sequence (append_many, attend_many, truncate, graphed_step_many). No MX
+    cache (its 64-token quantization windows are host-side state per
+    sequence).
 
     Where a local position lives is the subclass seam: the methods under
     "storage" below are all that PagedDecodeSession replaces.
@@ -460,6 +477,13 @@ class RaggedDecodeSession:
         self.totals = [0] * batch       # global tokens of each sequence
         self.local_lens = [0] * batch   # of them, in THIS rank's shard
         self._mask_cache: dict[tuple, torch.Tensor] = {}
+        # multi-token verify: (B, T) visible lengths per T (static buffers:
+        # a captured graph reads them), the device copies of counts seen,
+        # and (T, host vis, totals) after the last append_many: stale once
+        # the totals have moved on
+        self._vis_bufs: dict[int, torch.Tensor] = {}
+        self._counts_cache: dict[tuple, torch.Tensor] = {}
+        self._spec: tuple[int, list[list[int]], tuple] | None = None
         return td, _local_cap(max_tokens, block, self.world)
 
     # ---- storage: a (B, Hkv, capacity, D) slab ----
@@ -514,6 +538,22 @@ class RaggedDecodeSession:
         # chunk to its own row's length, read from local_len_dev
         return ext.flash_attention_cache(q.contiguous(), self.k, self.v,
                                          self.local_len_dev, scale)
+
+    def _launch_append_n(self, ext, k_new, v_new, counts_dev, vis_dev) -> None:
+        ext.kv_cache_append_n(
+            self.k, self.v, k_new.to(self.k.dtype).contiguous(),
+            v_new.to(self.v.dtype).contiguous(), self.total_dev,
+            self.local_len_dev, counts_dev, vis_dev, self.block, self.rank,
+            self.world)
+
+    def _launch_attend_many(self, ext, q, scale: float, vis_dev):
+        return ext.flash_attention_cache_qlen(
+            q.contiguous(), self.k, self.v, self.local_len_dev, vis_dev,
+            scale)
+
+    def _release(self, b: int) -> None:
+        """Row b's local length shrank: give back what it no longer needs.
+        The slab keeps every position."""
 
     # ---- host mirror ----
     def _mask(self, active) -> list[bool]:
@@ -646,6 +686,132 @@ class RaggedDecodeSession:
         self.local_lens[b] = 0
         self._push_lengths(b)
 
+    # ---- multi-token verify step: cache updates ----
+    def _counts(self, counts, t: int) -> list[int]:
+        if counts is None:
+            return [t] * self.batch
+        if isinstance(counts, torch.Tensor):
+            counts = counts.tolist()
+        counts = [int(c) for c in counts]
+        if len(counts) != self.batch:
+            raise ValueError(f"counts has {len(counts)} entries for a batch "
+                             f"of {self.batch}")
+        for b, c in enumerate(counts):
+            if not 0 <= c <= t:
+                raise ValueError(f"counts[{b}] = {c} is outside [0, {t}]")
+        return counts
+
+    def _counts_dev(self, counts: list[int]) -> torch.Tensor:
+        """counts as a (B,) int32 device tensor, from a small cache
+        (_mask_dev)."""
+        key = tuple(counts)
+        dev = self._counts_cache.get(key)
+        if dev is None:
+            if len(self._counts_cache) >= 256:
+                self._counts_cache.clear()
+            dev = torch.tensor(counts, dtype=torch.int32).to(self.device)
+            self._counts_cache[key] = dev
+        return dev
+
+    def _vis_dev(self, t: int) -> torch.Tensor:
+        """The (B, t) int64 device buffer of visible lengths: one per t, so
+        a captured graph and the eager calls share it."""
+        buf = self._vis_bufs.get(t)
+        if buf is None:
+            buf = torch.zeros(self.batch, t, dtype=torch.long,
+                              device=self.device)
+            self._vis_bufs[t] = buf
+        return buf
+
+    def _check_many(self, k_new: torch.Tensor, v_new: torch.Tensor) -> int:
+        kv = self._kv
+        if (k_new.dim() != 4 or k_new.shape != v_new.shape
+                or k_new.shape[0] != self.batch
+                or k_new.shape[1] != kv.size(1)
+                or k_new.shape[3] != kv.size(3)
+                or not 1 <= k_new.shape[2] <= 16):
+            raise ValueError(
+                f"append_many: k_new / v_new must be (B, Hkv, T, D) = "
+                f"({self.batch}, {kv.size(1)}, T, {kv.size(3)}) with T in "
+                f"1..16, got {tuple(k_new.shape)} / {tuple(v_new.shape)}")
+        return k_new.shape[2]
+
+    def _many_ends(self, counts: list[int]) -> dict[int, int]:
+        """_step_ends for counts[b] tokens per row: the capacity check, then
+        the rows whose shard grows -> the local positions they will hold."""
+        ends, cap = {}, self.capacity
+        for b, c in enumerate(counts):
+            end = _n_local(self.totals[b] + c, self.block, self.rank,
+                           self.world)
+            if end == self.local_lens[b]:
+                continue
+            if end > cap:
+                raise RuntimeError(
+                    f"{type(self).__name__} capacity exceeded: row {b} local "
+                    f"shard full at {self.local_lens[b]} tokens (grow "
+                    f"max_tokens)")
+            ends[b] = end
+        return ends
+
+    def _advance_many(self, counts: list[int], t: int) -> None:
+        """The mirror after counts[b] of t tokens per row, and the visible
+        lengths kv_append_n_kernel leaves: query i of row b sees the tokens
+        before this step and drafts 0..min(i, counts[b] - 1)."""
+        vis = []
+        for b, c in enumerate(counts):
+            t0 = self.totals[b]
+            vis.append([
+                _n_local(t0 + (min(i, c - 1) + 1 if c else 0), self.block,
+                         self.rank, self.world) for i in range(t)])
+            if c:
+                self.local_lens[b] = _n_local(t0 + c, self.block, self.rank,
+                                              self.world)
+            self.totals[b] = t0 + c
+        self._spec = (t, vis, tuple(self.totals))
+
+    def append_many(self, k_new: torch.Tensor, v_new: torch.Tensor,
+                    counts=None) -> None:
+        """Append up to T draft tokens per sequence, (B, Hkv, T, D): row b
+        takes its first counts[b] (host ints in [0, T]; None: T for every
+        row). Every rank calls this with the same arguments; only a token's
+        owning rank stores it. attend_many() then verifies the drafts and
+        truncate() takes the rejected ones back out."""
+        t = self._check_many(k_new, v_new)
+        counts = self._counts(counts, t)
+        self._reserve(self._many_ends(counts))
+        vis_dev = self._vis_dev(t)
+        if self._append_kernel_ok():
+            self._launch_append_n(self._ext(), k_new, v_new,
+                                  self._counts_dev(counts), vis_dev)
+            self._advance_many(counts, t)
+            return
+        for b, c in enumerate(counts):
+            for i in range(c):
+                owner, pos = _place(self.totals[b] + i, self.block,
+                                    self.world)
+                if owner == self.rank:
+                    self._store(b, pos, k_new[b, :, i : i + 1],
+                                v_new[b, :, i : i + 1])
+        self._advance_many(counts, t)
+        self.total_dev.copy_(torch.tensor(self.totals, dtype=torch.long))
+        self.local_len_dev.copy_(torch.tensor(self.local_lens,
+                                              dtype=torch.long))
+        vis_dev.copy_(torch.tensor(self._spec[1], dtype=torch.long))
+
+    def truncate(self, b: int, total: int) -> None:
+        """Cut sequence b back to its first `total` tokens (the rejected
+        drafts of a verify step): lengths on host and device; nothing is
+        cleared. A paged session hands back the pages past the new length."""
+        if not 0 <= total <= self.totals[b]:
+            raise ValueError(
+                f"truncate: row {b} holds {self.totals[b]} tokens, cannot "
+                f"cut to {total}")
+        self.totals[b] = total
+        self.local_lens[b] = _n_local(total, self.block, self.rank,
+                                      self.world)
+        self._push_lengths(b)
+        self._release(b)
+
     # ---- attention ----
     def _local_partial(self, q: torch.Tensor, softmax_scale: float | None):
         if _zero_copy_ok(q, self._kv):
@@ -669,6 +835,59 @@ class RaggedDecodeSession:
         tokens -> (B, Hq, 1, D). A sequence that holds no token yields an
         all-zero row."""
         out_l, lse_l = self._local_partial(q, softmax_scale)
+        out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
+        return out
+
+    def _local_partial_many(self, q: torch.Tensor, vis: list[list[int]],
+                            softmax_scale: float | None):
+        if _zero_copy_ok(q, self._kv, any_tq=True):
+            return self._launch_attend_many(
+                self._ext(), q, _scale(softmax_scale, q),
+                self._vis_dev(q.shape[2]))
+        # per row and per run of query positions with one visible length
+        t = q.shape[2]
+        outs, lses = [], []
+        for b in range(self.batch):
+            row_o, row_l, i = [], [], 0
+            while i < t:
+                n, j = vis[b][i], i + 1
+                while j < t and vis[b][j] == n:
+                    j += 1
+                qb = q[b : b + 1, :, i:j]
+                if n > 0:
+                    k, v = self._fallback_rows(qb, b, n)
+                    if q.device.type == "cuda" and k.dtype == torch.float32:
+                        # the GPU kernels take no fp32 K/V
+                        k, v = k.to(q.dtype), v.to(q.dtype)
+                    o, l = local_attention(qb, k, v, softmax_scale)
+                else:
+                    o, l = _empty_partial(qb)
+                row_o.append(o)
+                row_l.append(l)
+                i = j
+            outs.append(torch.cat(row_o, dim=2))
+            lses.append(torch.cat(row_l, dim=2))
+        return torch.cat(outs), torch.cat(lses)
+
+    def attend_many(self, q: torch.Tensor,
+                    softmax_scale: float | None = None,
+                    combine: str = "auto") -> torch.Tensor:
+        """Verify the drafts of the last append_many: q (B, Hq, T, D) ->
+        (B, Hq, T, D). Query i of sequence b attends the tokens b held
+        before that append plus drafts 0..min(i, counts[b] - 1): rows at or
+        past counts[b] see what the last draft sees, a row with count 0 the
+        whole sequence. A sequence that holds no token yields zeros."""
+        spec = self._spec
+        if spec is None or spec[2] != tuple(self.totals):
+            raise RuntimeError(
+                "attend_many: no append_many since the lengths last moved")
+        t, vis, _ = spec
+        if q.dim() != 4 or q.shape[0] != self.batch or q.shape[2] != t:
+            raise ValueError(
+                f"attend_many: q must be (B, Hq, T, D) with B = {self.batch} "
+                f"and the T = {t} of the last append_many, got "
+                f"{tuple(q.shape)}")
+        out_l, lse_l = self._local_partial_many(q, vis, softmax_scale)
         out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
         return out
 
@@ -721,6 +940,70 @@ class RaggedDecodeSession:
             if mask != in_buffer[0]:   # a steady mask costs no copy at all
                 active_dev.copy_(self._mask_dev(mask))
                 in_buffer[0] = mask
+            graph.replay()
+            if self.world == 1:
+                return out_l
+            out, _ = tree_combine(out_l, lse_l, strategy=combine,
+                                  group=self.group)
+            return out
+
+        return replay
+
+    def graphed_step_many(self, q_static: torch.Tensor,
+                          k_static: torch.Tensor, v_static: torch.Tensor,
+                          softmax_scale: float | None = None,
+                          combine: str = "auto"):
+        """graphed_step for a verify step of T tokens per row: the
+        multi-token append kernel, the visible-length cache kernel(s) and
+        the split combine, one linear chain, captured under an all-zero
+        ``counts``. Returns ``replay``.
+
+        Write the queries (B, Hq, T, D) and the drafts' K/V (B, Hkv, T, D)
+        into the static tensors, then ``replay(counts=None)`` checks
+        capacity on the host mirror, reserves, advances the mirror, copies
+        ``counts`` into the static device buffer when they changed, replays
+        and returns the output as graphed_step does. truncate() between
+        replays is legal: the lengths are device buffers the replay reads.
+        """
+        if self.device.type != "cuda":
+            raise ValueError("graphed_step needs a GPU session")
+        if not _zero_copy_ok(q_static, self._kv, any_tq=True):
+            raise ValueError(self._graph_refusal)
+        if not self._append_kernel_ok():
+            raise ValueError("graphed_step: the append kernel needs cache "
+                             "rows of a multiple of 4 bytes")
+        t = self._check_many(k_static, v_static)
+        if q_static.dim() != 4 or q_static.shape[0] != self.batch or \
+                q_static.shape[2] != t:
+            raise ValueError(
+                f"graphed_step_many: q_static must be (B, Hq, T, D) with "
+                f"B = {self.batch} and the T = {t} of k_static, got "
+                f"{tuple(q_static.shape)}")
+        ext = self._ext()
+        counts_dev = torch.zeros(self.batch, dtype=torch.int32,
+                                 device=self.device)
+        vis_dev = self._vis_dev(t)
+        scale = _scale(softmax_scale, q_static)
+
+        def step():
+            self._launch_append_n(ext, k_static, v_static, counts_dev,
+                                  vis_dev)
+            return self._launch_attend_many(ext, q_static, scale, vis_dev)
+
+        # the warm-up runs under all-zero counts, so no length moves
+        graph, (out_l, lse_l) = _capture(step)
+        self._graph_many = graph  # keep alive
+        self._counts_static = counts_dev
+
+        in_buffer = [[0] * self.batch]   # what counts_dev holds now
+
+        def replay(counts=None) -> torch.Tensor:
+            counts = self._counts(counts, t)
+            self._reserve(self._many_ends(counts))
+            self._advance_many(counts, t)
+            if counts != in_buffer[0]:
+                counts_dev.copy_(self._counts_dev(counts))
+                in_buffer[0] = counts
             graph.replay()
             if self.world == 1:
                 return out_l
@@ -881,6 +1164,27 @@ class PagedDecodeSession(RaggedDecodeSession):
         return ext.flash_attention_paged(
             q.contiguous(), self.k_pool, self.v_pool, self.page_table,
             self.local_len_dev, scale)
+
+    def _launch_append_n(self, ext, k_new, v_new, counts_dev, vis_dev) -> None:
+        ext.kv_pool_append_n(
+            self.k_pool, self.v_pool, self.page_table,
+            k_new.to(self.k_pool.dtype).contiguous(),
+            v_new.to(self.v_pool.dtype).contiguous(), self.total_dev,
+            self.local_len_dev, counts_dev, vis_dev, self.block, self.rank,
+            self.world)
+
+    def _launch_attend_many(self, ext, q, scale: float, vis_dev):
+        return ext.flash_attention_paged_qlen(
+            q.contiguous(), self.k_pool, self.v_pool, self.page_table,
+            self.local_len_dev, vis_dev, scale)
+
+    def _release(self, b: int) -> None:
+        """The pages past ceil(local_len / page) go back to the free list,
+        the next ones handed out and in reset()'s order; their stale table
+        entries are never read."""
+        keep = (self.local_lens[b] + self._page - 1) // self._page
+        self._free.extend(reversed(self._pages[b][keep:]))
+        del self._pages[b][keep:]
 
     def reset(self, b: int) -> None:
         """Free slot b for a new sequence: its lengths go to 0 on host and
