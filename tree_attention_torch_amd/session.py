@@ -76,6 +76,27 @@ def _n_local(t: int, block: int, rank: int, world: int) -> int:
             + (t % block if full % world == rank else 0))
 
 
+def _tree_masks(t0: int, cnt: int, parents: list[int], t: int, block: int,
+                rank: int, world: int) -> tuple[int, list[int]]:
+    """(base, masks) of one row of a tree append, as kv_append_tree_kernel
+    leaves them: base = _n_local(t0); bit s of masks[i] is set when the
+    draft node at local slot s (local position base + s) is query i's own
+    node or one of its ancestors and `rank` owns it. The walk i ->
+    parents[i] -> ... clamps every step into [-1, node - 1], so it ends
+    whatever the table holds; queries at or past cnt get 0."""
+    base = _n_local(t0, block, rank, world)
+    masks = []
+    for i in range(t):
+        m, n = 0, (i if i < cnt else -1)
+        while n >= 0:
+            if _place(t0 + n, block, world)[0] == rank:
+                m |= 1 << (_n_local(t0 + n + 1, block, rank, world) - 1
+                           - base)
+            n = min(max(int(parents[n]), -1), n - 1)
+        masks.append(m)
+    return base, masks
+
+
 def _empty_partial(q: torch.Tensor):
     """The partial of a shard that holds no key: out = 0, lse = -inf."""
     b, hq, tq, d = q.shape
@@ -427,7 +448,9 @@ class RaggedDecodeSession:
 
     ``max_tokens`` is per sequence. attend() takes one query row per
     sequence; a speculative verify step takes up to 16 draft tokens per
-    sequence (append_many, attend_many, truncate, graphed_step_many). No MX
+    sequence, as a chain (append_many, attend_many, truncate,
+    graphed_step_many) or as a token tree (append_tree, attend_tree, commit,
+    graphed_step_tree). No MX
     cache (its 64-token quantization windows are host-side state per
     sequence).
 
@@ -484,6 +507,13 @@ class RaggedDecodeSession:
         self._vis_bufs: dict[int, torch.Tensor] = {}
         self._counts_cache: dict[tuple, torch.Tensor] = {}
         self._spec: tuple[int, list[list[int]], tuple] | None = None
+        # tree-shaped drafts: (base (B,) int64, mask (B, T) int32) static
+        # buffers per T, and the pending tree of the last append_tree (its
+        # cast drafts, counts, parents, the totals before and after). Every
+        # method that moves a length drops it; the totals are compared as
+        # well, as for _spec
+        self._tree_bufs: dict[int, tuple[torch.Tensor, torch.Tensor]] = {}
+        self._tree: dict | None = None
         return td, _local_cap(max_tokens, block, self.world)
 
     # ---- storage: a (B, Hkv, capacity, D) slab ----
@@ -550,6 +580,26 @@ class RaggedDecodeSession:
         return ext.flash_attention_cache_qlen(
             q.contiguous(), self.k, self.v, self.local_len_dev, vis_dev,
             scale)
+
+    def _launch_append_tree(self, ext, k_new, v_new, counts_dev, parents_dev,
+                            base_dev, mask_dev) -> None:
+        # k_new / v_new arrive cast and contiguous (_cast_new)
+        ext.kv_cache_append_tree(
+            self.k, self.v, k_new, v_new, self.total_dev, self.local_len_dev,
+            counts_dev, parents_dev, base_dev, mask_dev, self.block,
+            self.rank, self.world)
+
+    def _launch_attend_tree(self, ext, q, scale: float, base_dev, mask_dev):
+        return ext.flash_attention_cache_tree(
+            q.contiguous(), self.k, self.v, self.local_len_dev, base_dev,
+            mask_dev, scale)
+
+    def _launch_commit(self, ext, k_new, v_new, counts_dev, path_dev,
+                       lens_dev) -> None:
+        ext.kv_cache_commit_path(
+            self.k, self.v, k_new, v_new, self.total_dev, self.local_len_dev,
+            counts_dev, path_dev, lens_dev, self.block, self.rank,
+            self.world)
 
     def _release(self, b: int) -> None:
         """Row b's local length shrank: give back what it no longer needs.
@@ -652,6 +702,7 @@ class RaggedDecodeSession:
             t += n
         if chunks:
             self._reserve({b: max(pos + n for _, n, pos in chunks)})
+        self._tree = None
         for t, n, pos in chunks:
             self._store(b, pos, k_seq[:, t : t + n], v_seq[:, t : t + n])
             self.local_lens[b] = pos + n
@@ -667,6 +718,7 @@ class RaggedDecodeSession:
         mask = self._mask(active)
         ends = self._step_ends(mask)
         self._reserve(ends)
+        self._tree = None
         if self._append_kernel_ok():
             self._launch_append(self._ext(), k_new, v_new,
                                 self._mask_dev(mask))
@@ -682,6 +734,7 @@ class RaggedDecodeSession:
     def reset(self, b: int) -> None:
         """Free slot b for a new sequence: its lengths go to 0 on host and
         device; nothing is cleared."""
+        self._tree = None
         self.totals[b] = 0
         self.local_lens[b] = 0
         self._push_lengths(b)
@@ -723,7 +776,8 @@ class RaggedDecodeSession:
             self._vis_bufs[t] = buf
         return buf
 
-    def _check_many(self, k_new: torch.Tensor, v_new: torch.Tensor) -> int:
+    def _check_many(self, k_new: torch.Tensor, v_new: torch.Tensor,
+                    who: str = "append_many") -> int:
         kv = self._kv
         if (k_new.dim() != 4 or k_new.shape != v_new.shape
                 or k_new.shape[0] != self.batch
@@ -731,7 +785,7 @@ class RaggedDecodeSession:
                 or k_new.shape[3] != kv.size(3)
                 or not 1 <= k_new.shape[2] <= 16):
             raise ValueError(
-                f"append_many: k_new / v_new must be (B, Hkv, T, D) = "
+                f"{who}: k_new / v_new must be (B, Hkv, T, D) = "
                 f"({self.batch}, {kv.size(1)}, T, {kv.size(3)}) with T in "
                 f"1..16, got {tuple(k_new.shape)} / {tuple(v_new.shape)}")
         return k_new.shape[2]
@@ -779,6 +833,7 @@ class RaggedDecodeSession:
         t = self._check_many(k_new, v_new)
         counts = self._counts(counts, t)
         self._reserve(self._many_ends(counts))
+        self._tree = None
         vis_dev = self._vis_dev(t)
         if self._append_kernel_ok():
             self._launch_append_n(self._ext(), k_new, v_new,
@@ -806,11 +861,262 @@ class RaggedDecodeSession:
             raise ValueError(
                 f"truncate: row {b} holds {self.totals[b]} tokens, cannot "
                 f"cut to {total}")
+        self._tree = None
         self.totals[b] = total
         self.local_lens[b] = _n_local(total, self.block, self.rank,
                                       self.world)
         self._push_lengths(b)
         self._release(b)
+
+    # ---- tree-shaped drafts: append, verify, keep the accepted path ----
+    def _tree_dev(self, t: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """The (B,) int64 base and (B, t) int32 mask device buffers: one
+        pair per t, so a captured graph and the eager calls share them
+        (_vis_dev)."""
+        bufs = self._tree_bufs.get(t)
+        if bufs is None:
+            bufs = (torch.zeros(self.batch, dtype=torch.long,
+                                device=self.device),
+                    torch.zeros(self.batch, t, dtype=torch.int32,
+                                device=self.device))
+            self._tree_bufs[t] = bufs
+        return bufs
+
+    def _cast_new(self, k_new: torch.Tensor, v_new: torch.Tensor):
+        """The drafts as the cache stores them: what the append and the
+        commit kernels copy from."""
+        dtype = self._kv.dtype
+        return k_new.to(dtype).contiguous(), v_new.to(dtype).contiguous()
+
+    def _node_table(self, who: str, name: str, table, t: int, check,
+                    pad: int = -1) -> tuple[torch.Tensor, list | None]:
+        """`table` (parents or paths) as a (B, t) int32 device tensor plus
+        its host rows when it came as a nested list; a list is validated row
+        by row with check(b, row) and padded to t with `pad`."""
+        if isinstance(table, torch.Tensor):
+            if (table.dtype != torch.int32
+                    or table.device != self.total_dev.device
+                    or tuple(table.shape) != (self.batch, t)):
+                raise ValueError(
+                    f"{who}: {name} must be a (B, T) = ({self.batch}, {t}) "
+                    f"int32 tensor on {self.device}, got "
+                    f"{tuple(table.shape)} {table.dtype} on {table.device}")
+            return table.contiguous(), None
+        rows = [[int(p) for p in row] for row in table]
+        if len(rows) != self.batch:
+            raise ValueError(f"{who}: {name} has {len(rows)} rows for a "
+                             f"batch of {self.batch}")
+        for b, row in enumerate(rows):
+            if len(row) > t:
+                raise ValueError(f"{who}: {name}[{b}] has {len(row)} entries "
+                                 f"for T = {t}")
+            check(b, row)
+        host = [row + [pad] * (t - len(row)) for row in rows]
+        dev = torch.tensor(host, dtype=torch.int32).to(self.device)
+        return dev, host
+
+    def _fresh_tree(self, who: str) -> dict:
+        tree = self._tree
+        if tree is None or tree["totals"] != tuple(self.totals):
+            raise RuntimeError(
+                f"{who}: no append_tree since the lengths last moved")
+        return tree
+
+    def _tree_parents(self, tree: dict) -> list[list[int]]:
+        if tree["parents"] is None:
+            tree["parents"] = tree["parents_dev"].tolist()
+        return tree["parents"]
+
+    def _advance_tree(self, counts: list[int], t: int, k_c, v_c,
+                      parents_dev, parents_host) -> None:
+        t0 = list(self.totals)
+        self._advance_many(counts, t)
+        self._spec = None
+        self._tree = {"t": t, "k": k_c, "v": v_c, "counts": counts, "t0": t0,
+                      "totals": tuple(self.totals),
+                      "parents_dev": parents_dev, "parents": parents_host}
+
+    def append_tree(self, k_new: torch.Tensor, v_new: torch.Tensor, parents,
+                    counts=None) -> None:
+        """Append up to T draft NODES of a token tree per sequence, (B, Hkv,
+        T, D) in topological order: row b takes its first counts[b] (host
+        ints; None: T). ``parents`` is a (B, T) int32 tensor on the
+        session's device (a sampler's output goes straight through, no host
+        copy) or a nested list, which is validated; parents[b][j] in [-1, j
+        - 1] is node j's parent, -1 the last committed token. attend_tree()
+        then verifies every node against its own ancestors and commit()
+        keeps the accepted root-to-node path."""
+        t = self._check_many(k_new, v_new, "append_tree")
+        counts = self._counts(counts, t)
+
+        def check(b, row):
+            if len(row) < counts[b]:
+                raise ValueError(
+                    f"append_tree: parents[{b}] has {len(row)} entries for "
+                    f"counts[{b}] = {counts[b]}")
+            for j, p in enumerate(row):
+                if not -1 <= p < j:
+                    raise ValueError(
+                        f"append_tree: parents[{b}][{j}] = {p} is outside "
+                        f"[-1, {j - 1}] (row {b})")
+
+        parents_dev, parents_host = self._node_table(
+            "append_tree", "parents", parents, t, check)
+        self._reserve(self._many_ends(counts))
+        k_c, v_c = self._cast_new(k_new, v_new)
+        base_dev, mask_dev = self._tree_dev(t)
+        if self._append_kernel_ok():
+            self._launch_append_tree(self._ext(), k_c, v_c,
+                                     self._counts_dev(counts), parents_dev,
+                                     base_dev, mask_dev)
+            self._advance_tree(counts, t, k_c, v_c, parents_dev,
+                               parents_host)
+            return
+        for b, c in enumerate(counts):
+            for i in range(c):
+                owner, pos = _place(self.totals[b] + i, self.block,
+                                    self.world)
+                if owner == self.rank:
+                    self._store(b, pos, k_c[b, :, i : i + 1],
+                                v_c[b, :, i : i + 1])
+        self._advance_tree(counts, t, k_c, v_c, parents_dev, parents_host)
+        self.total_dev.copy_(torch.tensor(self.totals, dtype=torch.long))
+        self.local_len_dev.copy_(torch.tensor(self.local_lens,
+                                              dtype=torch.long))
+        bases, masks = self._tree_host(self._tree)
+        base_dev.copy_(torch.tensor(bases, dtype=torch.long))
+        mask_dev.copy_(torch.tensor(masks, dtype=torch.int32))
+
+    def _tree_host(self, tree: dict):
+        """(bases, masks) of the pending tree on the host: _tree_masks per
+        row."""
+        parents = self._tree_parents(tree)
+        rows = [_tree_masks(tree["t0"][b], c, parents[b], tree["t"],
+                            self.block, self.rank, self.world)
+                for b, c in enumerate(tree["counts"])]
+        return [r[0] for r in rows], [r[1] for r in rows]
+
+    def _local_partial_tree(self, q: torch.Tensor, tree: dict,
+                            softmax_scale: float | None):
+        t = tree["t"]
+        if _zero_copy_ok(q, self._kv, any_tq=True):
+            base_dev, mask_dev = self._tree_dev(t)
+            return self._launch_attend_tree(
+                self._ext(), q, _scale(softmax_scale, q), base_dev, mask_dev)
+        # per row and per run of query positions with one mask: gather the
+        # visible local rows (the prefix plus the owned ancestors)
+        bases, masks = self._tree_host(tree)
+        outs, lses = [], []
+        for b in range(self.batch):
+            base, row_o, row_l, i = bases[b], [], [], 0
+            while i < t:
+                m, j = masks[b][i], i + 1
+                while j < t and masks[b][j] == m:
+                    j += 1
+                qb = q[b : b + 1, :, i:j]
+                slots = [s for s in range(16) if (m >> s) & 1]
+                n = base + len(slots)
+                if n > 0:
+                    last = base + slots[-1] + 1 if slots else base
+                    k, v = self._fallback_rows(qb, b, last)
+                    if slots != list(range(len(slots))):
+                        idx = torch.tensor(
+                            list(range(base)) + [base + s for s in slots],
+                            dtype=torch.long, device=k.device)
+                        k = k.index_select(2, idx)
+                        v = v.index_select(2, idx)
+                    if q.device.type == "cuda" and k.dtype == torch.float32:
+                        # the GPU kernels take no fp32 K/V
+                        k, v = k.to(q.dtype), v.to(q.dtype)
+                    o, l = local_attention(qb, k, v, softmax_scale)
+                else:
+                    o, l = _empty_partial(qb)
+                row_o.append(o)
+                row_l.append(l)
+                i = j
+            outs.append(torch.cat(row_o, dim=2))
+            lses.append(torch.cat(row_l, dim=2))
+        return torch.cat(outs), torch.cat(lses)
+
+    def attend_tree(self, q: torch.Tensor, softmax_scale: float | None = None,
+                    combine: str = "auto") -> torch.Tensor:
+        """Verify the nodes of the last append_tree: q (B, Hq, T, D) -> (B,
+        Hq, T, D). Query i < counts[b] of sequence b attends the tokens b
+        held before that append plus node i and its ancestors, never a
+        sibling; a query at or past counts[b] only the tokens before the
+        append. A row with nothing to see yields zeros."""
+        tree = self._fresh_tree("attend_tree")
+        t = tree["t"]
+        if q.dim() != 4 or q.shape[0] != self.batch or q.shape[2] != t:
+            raise ValueError(
+                f"attend_tree: q must be (B, Hq, T, D) with B = {self.batch} "
+                f"and the T = {t} of the last append_tree, got "
+                f"{tuple(q.shape)}")
+        out_l, lse_l = self._local_partial_tree(q, tree, softmax_scale)
+        out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
+        return out
+
+    def commit(self, paths, lens) -> None:
+        """Keep, per sequence, the accepted root-to-node path of the last
+        append_tree and drop the other drafts: nodes paths[b][:lens[b]]
+        become the sequence's next lens[b] tokens. ``paths`` is a (B, T)
+        int32 device tensor or a nested list, which is checked against the
+        parents to be a path from a root; ``lens`` are host ints in [0,
+        counts[b]] (0 rejects every draft), so the host mirror stays exact.
+        A paged session hands back the pages past the new lengths."""
+        tree = self._fresh_tree("commit")
+        t, counts = tree["t"], tree["counts"]
+        if isinstance(lens, torch.Tensor):
+            lens = lens.tolist()
+        lens = [int(n) for n in lens]
+        if len(lens) != self.batch:
+            raise ValueError(f"commit: lens has {len(lens)} entries for a "
+                             f"batch of {self.batch}")
+        for b, n in enumerate(lens):
+            if not 0 <= n <= counts[b]:
+                raise ValueError(f"commit: lens[{b}] = {n} is outside "
+                                 f"[0, {counts[b]}] (row {b})")
+
+        def check(b, row):
+            if len(row) < lens[b]:
+                raise ValueError(f"commit: paths[{b}] has {len(row)} entries "
+                                 f"for lens[{b}] = {lens[b]}")
+            parents, prev = self._tree_parents(tree)[b], -1
+            for i, node in enumerate(row[: lens[b]]):
+                if not 0 <= node < counts[b] or parents[node] != prev:
+                    raise ValueError(
+                        f"commit: paths[{b}][{i}] = {node} does not continue "
+                        f"a path from the root of row {b}'s tree")
+                prev = node
+
+        path_dev, path_host = self._node_table("commit", "paths", paths, t,
+                                               check, pad=0)
+        if self._append_kernel_ok():
+            self._launch_commit(self._ext(), tree["k"], tree["v"],
+                                self._counts_dev(counts), path_dev,
+                                self._counts_dev(lens))
+        else:
+            if path_host is None:
+                path_host = path_dev.tolist()
+            for b, n in enumerate(lens):
+                for i in range(n):
+                    src = min(max(path_host[b][i], 0), t - 1)
+                    owner, pos = _place(tree["t0"][b] + i, self.block,
+                                        self.world)
+                    if owner == self.rank:
+                        self._store(b, pos, tree["k"][b, :, src : src + 1],
+                                    tree["v"][b, :, src : src + 1])
+        for b, n in enumerate(lens):
+            self.totals[b] = tree["t0"][b] + n
+            self.local_lens[b] = _n_local(self.totals[b], self.block,
+                                          self.rank, self.world)
+        if not self._append_kernel_ok():
+            self.total_dev.copy_(torch.tensor(self.totals, dtype=torch.long))
+            self.local_len_dev.copy_(torch.tensor(self.local_lens,
+                                                  dtype=torch.long))
+        for b in range(self.batch):
+            self._release(b)
+        self._tree = None
 
     # ---- attention ----
     def _local_partial(self, q: torch.Tensor, softmax_scale: float | None):
@@ -936,6 +1242,7 @@ class RaggedDecodeSession:
         def replay(active=None) -> torch.Tensor:
             mask = self._mask(active)
             self._reserve(self._step_ends(mask))
+            self._tree = None
             self._advance(mask)
             if mask != in_buffer[0]:   # a steady mask costs no copy at all
                 active_dev.copy_(self._mask_dev(mask))
@@ -1000,7 +1307,87 @@ class RaggedDecodeSession:
         def replay(counts=None) -> torch.Tensor:
             counts = self._counts(counts, t)
             self._reserve(self._many_ends(counts))
+            self._tree = None
             self._advance_many(counts, t)
+            if counts != in_buffer[0]:
+                counts_dev.copy_(self._counts_dev(counts))
+                in_buffer[0] = counts
+            graph.replay()
+            if self.world == 1:
+                return out_l
+            out, _ = tree_combine(out_l, lse_l, strategy=combine,
+                                  group=self.group)
+            return out
+
+        return replay
+
+    def graphed_step_tree(self, q_static: torch.Tensor,
+                          k_static: torch.Tensor, v_static: torch.Tensor,
+                          parents_static: torch.Tensor,
+                          softmax_scale: float | None = None,
+                          combine: str = "auto"):
+        """graphed_step_many for a tree of T draft nodes per row: the tree
+        append kernel, the ancestor-mask cache kernel(s) and the split
+        combine, one linear chain, captured under an all-zero ``counts``.
+        Returns ``replay``.
+
+        Write the queries (B, Hq, T, D), the nodes' K/V (B, Hkv, T, D) and
+        their parents (B, T) int32 into the static tensors, then
+        ``replay(counts=None)`` does what graphed_step_many's does and
+        leaves the step as the pending tree. commit() after a replay is an
+        eager launch and is legal between replays, as truncate() is.
+        """
+        if self.device.type != "cuda":
+            raise ValueError("graphed_step needs a GPU session")
+        if not _zero_copy_ok(q_static, self._kv, any_tq=True):
+            raise ValueError(self._graph_refusal)
+        if not self._append_kernel_ok():
+            raise ValueError("graphed_step: the append kernel needs cache "
+                             "rows of a multiple of 4 bytes")
+        t = self._check_many(k_static, v_static, "graphed_step_tree")
+        if q_static.dim() != 4 or q_static.shape[0] != self.batch or \
+                q_static.shape[2] != t:
+            raise ValueError(
+                f"graphed_step_tree: q_static must be (B, Hq, T, D) with "
+                f"B = {self.batch} and the T = {t} of k_static, got "
+                f"{tuple(q_static.shape)}")
+        if not isinstance(parents_static, torch.Tensor):
+            raise ValueError("graphed_step_tree: parents_static must be a "
+                             "(B, T) int32 device tensor")
+        parents_dev, _ = self._node_table("graphed_step_tree",
+                                          "parents_static", parents_static, t,
+                                          None)
+        if parents_dev is not parents_static:
+            raise ValueError("graphed_step_tree: parents_static must be "
+                             "contiguous")
+        ext = self._ext()
+        counts_dev = torch.zeros(self.batch, dtype=torch.int32,
+                                 device=self.device)
+        base_dev, mask_dev = self._tree_dev(t)
+        scale = _scale(softmax_scale, q_static)
+
+        def step():
+            # the cast drafts are what commit() copies from after a replay
+            k_c, v_c = self._cast_new(k_static, v_static)
+            self._launch_append_tree(ext, k_c, v_c, counts_dev, parents_dev,
+                                     base_dev, mask_dev)
+            return k_c, v_c, self._launch_attend_tree(ext, q_static, scale,
+                                                      base_dev, mask_dev)
+
+        # the warm-up runs under all-zero counts, so no length moves; it
+        # does rewrite the shared base / mask buffers of this T, so a tree
+        # pending from an eager append_tree ends here
+        self._tree = None
+        graph, (k_c, v_c, (out_l, lse_l)) = _capture(step)
+        self._graph_tree = graph  # keep alive
+        self._counts_static_tree = counts_dev
+
+        in_buffer = [[0] * self.batch]   # what counts_dev holds now
+
+        def replay(counts=None) -> torch.Tensor:
+            counts = self._counts(counts, t)
+            self._reserve(self._many_ends(counts))
+            self._advance_tree(counts, t, k_c, v_c, parents_dev, None)
             if counts != in_buffer[0]:
                 counts_dev.copy_(self._counts_dev(counts))
                 in_buffer[0] = counts
@@ -1177,6 +1564,25 @@ class PagedDecodeSession(RaggedDecodeSession):
         return ext.flash_attention_paged_qlen(
             q.contiguous(), self.k_pool, self.v_pool, self.page_table,
             self.local_len_dev, vis_dev, scale)
+
+    def _launch_append_tree(self, ext, k_new, v_new, counts_dev, parents_dev,
+                            base_dev, mask_dev) -> None:
+        ext.kv_pool_append_tree(
+            self.k_pool, self.v_pool, self.page_table, k_new, v_new,
+            self.total_dev, self.local_len_dev, counts_dev, parents_dev,
+            base_dev, mask_dev, self.block, self.rank, self.world)
+
+    def _launch_attend_tree(self, ext, q, scale: float, base_dev, mask_dev):
+        return ext.flash_attention_paged_tree(
+            q.contiguous(), self.k_pool, self.v_pool, self.page_table,
+            self.local_len_dev, base_dev, mask_dev, scale)
+
+    def _launch_commit(self, ext, k_new, v_new, counts_dev, path_dev,
+                       lens_dev) -> None:
+        ext.kv_pool_commit_path(
+            self.k_pool, self.v_pool, self.page_table, k_new, v_new,
+            self.total_dev, self.local_len_dev, counts_dev, path_dev,
+            lens_dev, self.block, self.rank, self.world)
 
     def _release(self, b: int) -> None:
         """The pages past ceil(local_len / page) go back to the free list,
