@@ -438,8 +438,8 @@ class RaggedDecodeSession:
     """Token-by-token decode of a BATCH whose sequences have their own
     lengths, over the same block-cyclic sharded cache as DecodeSession.
 
-    Sequences join (prefill), grow (append with an ``active`` mask) and
-    leave (reset) independently. The lengths live twice: ``total_dev`` /
+    Sequences join (prefill, or fork from another sequence's prefix), grow
+    (append with an ``active`` mask) and leave (reset) independently. The lengths live twice: ``total_dev`` /
     ``local_len_dev`` (B,) int64 on the device are what the kernels read, so
     a whole step (append kernel, cache kernel, split combine) replays from
     one hipGraph; ``totals`` / ``local_lens`` are the host mirror, advanced
@@ -605,6 +605,13 @@ class RaggedDecodeSession:
         """Row b's local length shrank: give back what it no longer needs.
         The slab keeps every position."""
 
+    def _share(self, src: int, dst: int, n_local: int) -> None:
+        """Row dst (empty) comes to hold row src's first n_local local
+        positions. The slab shares nothing: a device copy of the rows."""
+        if n_local:
+            self.k[dst, :, :n_local].copy_(self.k[src, :, :n_local])
+            self.v[dst, :, :n_local].copy_(self.v[src, :, :n_local])
+
     # ---- host mirror ----
     def _mask(self, active) -> list[bool]:
         if active is None:
@@ -738,6 +745,34 @@ class RaggedDecodeSession:
         self.totals[b] = 0
         self.local_lens[b] = 0
         self._push_lengths(b)
+
+    def fork(self, src: int, dst: int, tokens: int | None = None) -> None:
+        """Slot dst becomes a sequence holding the first ``tokens`` global
+        tokens of sequence src (None: all of them); whatever dst held is
+        dropped as by reset(dst). Every rank calls this with the same
+        arguments. A paged session shares src's pages by reference and copies
+        a shared tail page before the first write into it; the slab copies
+        the rows. The lengths go to the device, so a step captured before
+        the fork replays correctly after it."""
+        for name, slot in (("src", src), ("dst", dst)):
+            if not 0 <= slot < self.batch:
+                raise ValueError(f"fork: {name} = {slot} is outside "
+                                 f"[0, {self.batch})")
+        if src == dst:
+            raise ValueError(f"fork: src and dst are both row {src}")
+        if tokens is None:
+            tokens = self.totals[src]
+        if not 0 <= tokens <= self.totals[src]:
+            raise ValueError(
+                f"fork: row {src} holds {self.totals[src]} tokens, cannot "
+                f"fork its first {tokens}")
+        self.reset(dst)
+        self._spec = None
+        n_local = _n_local(tokens, self.block, self.rank, self.world)
+        self._share(src, dst, n_local)
+        self.totals[dst] = tokens
+        self.local_lens[dst] = n_local
+        self._push_lengths(dst)
 
     # ---- multi-token verify step: cache updates ----
     def _counts(self, counts, t: int) -> list[int]:
@@ -1091,6 +1126,9 @@ class RaggedDecodeSession:
 
         path_dev, path_host = self._node_table("commit", "paths", paths, t,
                                                check, pad=0)
+        # no copy-on-write here: the positions re-stored are ones the
+        # preceding append_tree wrote, so its _reserve made their pages
+        # exclusive, and fork() drops the pending tree
         if self._append_kernel_ok():
             self._launch_commit(self._ext(), tree["k"], tree["v"],
                                 self._counts_dev(counts), path_dev,
@@ -1423,7 +1461,11 @@ class PagedDecodeSession(RaggedDecodeSession):
     exact, so before each step the host knows which rows land on a new page:
     it takes the page and writes that one table entry with a stream-ordered
     device fill (no pageable host-to-device copy, no device-side
-    allocation). reset(b) hands row b's pages back. A pool that runs out and
+    allocation). reset(b) hands row b's pages back. fork() shares pages
+    between rows by reference: a per-page count says how many rows name a
+    page, a row copies a shared tail page before its first write into it
+    (_reserve), and a page returns to the free list when its last holder
+    lets go. A pool that runs out and
     a row at its ceiling both raise RuntimeError naming the row, before
     anything is launched or stored.
     """
@@ -1457,6 +1499,9 @@ class PagedDecodeSession(RaggedDecodeSession):
                                       device=self.device)
         self._pages: list[list[int]] = [[] for _ in range(batch)]
         self._free = list(range(n_pages - 1, -1, -1))   # pop() takes page 0
+        # rows that name each page (fork shares pages): on _free exactly
+        # when 0
+        self._refs = [0] * n_pages
 
     @property
     def page(self) -> int:
@@ -1469,6 +1514,11 @@ class PagedDecodeSession(RaggedDecodeSession):
     @property
     def free_pages(self) -> int:
         return len(self._free)
+
+    @property
+    def shared_pages(self) -> int:
+        """Pages that more than one row holds."""
+        return sum(1 for r in self._refs if r > 1)
 
     # ---- storage: (n_pages, Hkv, page, D) pools behind the page table ----
     _graph_refusal = (
@@ -1487,22 +1537,85 @@ class PagedDecodeSession(RaggedDecodeSession):
 
     def _reserve(self, ends: dict[int, int]) -> None:
         """Raise if the pool cannot give every row its pages (nothing is
-        taken then); else take them and write their table entries."""
-        left = len(self._free)
+        taken then); else take them and write their table entries.
+
+        Copy-on-write: row b writes at [local_lens[b], ends[b]), and
+        _release has handed back every page past its live length, so the
+        one page it can share with another row (fork) is the partial page
+        holding local_lens[b]. While another row names that page, b takes a
+        fresh one and the live rows are copied over, all rows' copies in
+        one launch, before this returns: ahead of the append launch or the
+        graph replay."""
+        page, left = self._page, len(self._free)
+        cow: dict[int, int] = {}     # row -> index of its shared tail page
+        going: dict[int, int] = {}   # page -> rows leaving it in this call
         for b, end in ends.items():
-            need = (end + self._page - 1) // self._page - len(self._pages[b])
+            need = max((end + page - 1) // page - len(self._pages[b]), 0)
+            at = self.local_lens[b]
+            if end > at and at % page:
+                pid = self._pages[b][at // page]
+                if self._refs[pid] - going.get(pid, 0) > 1:
+                    going[pid] = going.get(pid, 0) + 1
+                    cow[b] = at // page
+                    need += 1
             if need > left:
                 raise RuntimeError(
                     f"PagedDecodeSession pool exhausted: row {b} needs "
-                    f"{need} more page(s) of {self._page} tokens, {left} of "
+                    f"{need} more page(s) of {page} tokens, {left} of "
                     f"{self.n_pages} free (grow pool_tokens or reset a row)")
-            left -= max(need, 0)
+            left -= need
+        copies = []   # (shared page, the row's own page, live rows)
         for b, end in ends.items():
-            while len(self._pages[b]) * self._page < end:
-                pid = self._free.pop()
+            if b in cow:
+                j = cow[b]
+                old, pid = self._pages[b][j], self._take()
+                self._refs[old] -= 1
+                self._pages[b][j] = pid
+                self.page_table[b, j : j + 1].fill_(pid)
+                copies.append((old, pid, self.local_lens[b] % page))
+            while len(self._pages[b]) * page < end:
+                pid = self._take()
                 j = len(self._pages[b])
                 self._pages[b].append(pid)
                 self.page_table[b, j : j + 1].fill_(pid)
+        if copies:
+            self._copy_pages(copies)
+
+    def _take(self) -> int:
+        pid = self._free.pop()
+        self._refs[pid] = 1
+        return pid
+
+    def _drop(self, pids: list[int]) -> None:
+        """One row lets go of pids: a page no row names any more goes back
+        to the free list, the last of pids first (the next handed out)."""
+        for pid in reversed(pids):
+            self._refs[pid] -= 1
+            if self._refs[pid] == 0:
+                self._free.append(pid)
+
+    def _copy_pages(self, copies: list[tuple[int, int, int]]) -> None:
+        """The first `rows` rows of every head of page src into page dst,
+        K and V, for each (src, dst, rows)."""
+        if self._append_kernel_ok():
+            self._ext().kv_pool_copy_rows(
+                self.k_pool, self.v_pool, [c[0] for c in copies],
+                [c[1] for c in copies], [c[2] for c in copies])
+            return
+        for src, dst, rows in copies:
+            self.k_pool[dst, :, :rows] = self.k_pool[src, :, :rows]
+            self.v_pool[dst, :, :rows] = self.v_pool[src, :, :rows]
+
+    def _share(self, src: int, dst: int, n_local: int) -> None:
+        """Row dst (empty) takes the pages of row src's first n_local local
+        positions by reference: no KV byte moves and no page leaves the
+        free list. The table entries go device to device, in stream order."""
+        n = (n_local + self._page - 1) // self._page
+        self._pages[dst] = self._pages[src][:n]
+        for pid in self._pages[dst]:
+            self._refs[pid] += 1
+        if n:
+            self.page_table[dst, :n].copy_(self.page_table[src, :n])
 
     def _store(self, b: int, pos: int, k_rows: torch.Tensor,
                v_rows: torch.Tensor) -> None:
@@ -1585,17 +1698,18 @@ class PagedDecodeSession(RaggedDecodeSession):
             lens_dev, self.block, self.rank, self.world)
 
     def _release(self, b: int) -> None:
-        """The pages past ceil(local_len / page) go back to the free list,
-        the next ones handed out and in reset()'s order; their stale table
-        entries are never read."""
+        """The row lets go of the pages past ceil(local_len / page): those
+        no other row holds go back to the free list, the next ones handed
+        out and in reset()'s order; their stale table entries are never
+        read."""
         keep = (self.local_lens[b] + self._page - 1) // self._page
-        self._free.extend(reversed(self._pages[b][keep:]))
+        self._drop(self._pages[b][keep:])
         del self._pages[b][keep:]
 
     def reset(self, b: int) -> None:
         """Free slot b for a new sequence: its lengths go to 0 on host and
-        device and its pages back to the free list (the next ones handed
-        out); nothing is cleared."""
+        device and its pages, where no other row holds them, back to the
+        free list (the next ones handed out); nothing is cleared."""
         super().reset(b)
-        self._free.extend(reversed(self._pages[b]))
+        self._drop(self._pages[b])
         self._pages[b] = []
