@@ -1173,12 +1173,27 @@ class RaggedDecodeSession:
             lses.append(l)
         return torch.cat(outs), torch.cat(lses)
 
+    def _check_shared(self, q: torch.Tensor) -> None:
+        """Whether this session takes shared=True under query q."""
+        raise ValueError(
+            f"{type(self).__name__}: shared=True needs a PagedDecodeSession; "
+            "the slab shares nothing between rows")
+
+    def _local_partial_shared(self, q: torch.Tensor,
+                              softmax_scale: float | None):
+        self._check_shared(q)
+
     def attend(self, q: torch.Tensor, softmax_scale: float | None = None,
-               combine: str = "auto") -> torch.Tensor:
+               combine: str = "auto", shared: bool = False) -> torch.Tensor:
         """Attention of q (B, Hq, 1, D), row b over sequence b's cached
         tokens -> (B, Hq, 1, D). A sequence that holds no token yields an
-        all-zero row."""
-        out_l, lse_l = self._local_partial(q, softmax_scale)
+        all-zero row. ``shared`` (PagedDecodeSession only): rows that hold
+        the same leading full pages attend them in one KV stream per group
+        (shared_plan) and their remainders on their own; same result."""
+        if shared:
+            out_l, lse_l = self._local_partial_shared(q, softmax_scale)
+        else:
+            out_l, lse_l = self._local_partial(q, softmax_scale)
         out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
         return out
 
@@ -1238,9 +1253,13 @@ class RaggedDecodeSession:
     def graphed_step(self, q_static: torch.Tensor, k_static: torch.Tensor,
                      v_static: torch.Tensor,
                      softmax_scale: float | None = None,
-                     combine: str = "auto"):
+                     combine: str = "auto", shared: bool = False):
         """Capture one decode step — append kernel, cache kernel, split
         combine, one linear chain — into a hipGraph. Returns ``replay``.
+        ``shared`` (PagedDecodeSession only): the chain is append kernel,
+        prefix pass, suffix pass, combine (attend(shared=True)); replay()
+        brings the device copy of shared_plan() up to date first, so a fork,
+        reset or truncate after the capture replays correctly.
 
         Write the step's query and new K/V (B, Hkv, 1, D) into the static
         tensors, then ``replay(active=None)`` checks capacity on the host
@@ -1252,6 +1271,8 @@ class RaggedDecodeSession:
         size > 1 the local partial replays from the graph and the collective
         runs eagerly (graphed_attend).
         """
+        if shared:
+            self._check_shared(q_static)
         if self.device.type != "cuda":
             raise ValueError("graphed_step needs a GPU session")
         # never capture the per-row fallback: it would freeze the
@@ -1265,9 +1286,15 @@ class RaggedDecodeSession:
         active_dev = torch.zeros(self.batch, dtype=torch.uint8,
                                  device=self.device)
         scale = _scale(softmax_scale, q_static)
+        hq = q_static.shape[1]
+        # static buffers: the capture reads them, replay() refreshes them
+        tables = self._shared_tables(hq) if shared else None
 
         def step():
             self._launch_append(ext, k_static, v_static, active_dev)
+            if shared:
+                return self._launch_attend_shared(ext, q_static, scale,
+                                                  tables)
             return self._launch_attend(ext, q_static, scale)
 
         # the warm-up runs under the all-zero mask, so no length moves
@@ -1285,6 +1312,8 @@ class RaggedDecodeSession:
             if mask != in_buffer[0]:   # a steady mask costs no copy at all
                 active_dev.copy_(self._mask_dev(mask))
                 in_buffer[0] = mask
+            if shared:   # the plan of the lengths the step will leave
+                self._shared_tables(hq)
             graph.replay()
             if self.world == 1:
                 return out_l
@@ -1502,6 +1531,13 @@ class PagedDecodeSession(RaggedDecodeSession):
         # rows that name each page (fork shares pages): on _free exactly
         # when 0
         self._refs = [0] * n_pages
+        # shared-prefix decode: _page_moves counts the pages that changed
+        # hands (with each row's number of full pages it tells whether
+        # shared_plan() can have changed); per Hq the plan last uploaded and
+        # its device tables (static buffers: a captured graph reads them)
+        self._page_moves = 0
+        self._shared: dict[int, dict] = {}
+        self.shared_plan_uploads = 0
 
     @property
     def page(self) -> int:
@@ -1584,11 +1620,13 @@ class PagedDecodeSession(RaggedDecodeSession):
     def _take(self) -> int:
         pid = self._free.pop()
         self._refs[pid] = 1
+        self._page_moves += 1
         return pid
 
     def _drop(self, pids: list[int]) -> None:
         """One row lets go of pids: a page no row names any more goes back
         to the free list, the last of pids first (the next handed out)."""
+        self._page_moves += len(pids)
         for pid in reversed(pids):
             self._refs[pid] -= 1
             if self._refs[pid] == 0:
@@ -1612,6 +1650,7 @@ class PagedDecodeSession(RaggedDecodeSession):
         free list. The table entries go device to device, in stream order."""
         n = (n_local + self._page - 1) // self._page
         self._pages[dst] = self._pages[src][:n]
+        self._page_moves += n
         for pid in self._pages[dst]:
             self._refs[pid] += 1
         if n:
@@ -1664,6 +1703,154 @@ class PagedDecodeSession(RaggedDecodeSession):
         return ext.flash_attention_paged(
             q.contiguous(), self.k_pool, self.v_pool, self.page_table,
             self.local_len_dev, scale)
+
+    # ---- shared-prefix decode ----
+    def _check_shared(self, q: torch.Tensor) -> None:
+        hkv = self.k_pool.size(1)
+        if q.dim() != 4 or q.shape[0] != self.batch or q.shape[2] != 1:
+            raise ValueError(
+                f"shared=True takes one query per row: q must be (B, Hq, 1, "
+                f"D) with B = {self.batch}, got {tuple(q.shape)}")
+        if q.shape[1] % hkv or q.shape[1] // hkv > 16:
+            raise ValueError(
+                f"shared=True needs Hq a multiple of Hkv = {hkv} and Hq/Hkv "
+                f"<= 16, got Hq = {q.shape[1]}")
+
+    def shared_plan(self, q_heads: int | None = None
+                    ) -> list[tuple[list[int], int]]:
+        """The groups of attend(shared=True) under ``q_heads`` query heads
+        (None: one per KV head): a list of (rows, prefix) in which every row
+        appears exactly once. The rows of a group hold the same pages for
+        their first ``prefix`` local tokens, whole pages all of them, and the
+        group's first row is the one whose page table the prefix is read
+        through. Host-side and per rank: it is over this rank's local pages.
+
+        Page j of row b is full when local_lens[b] >= (j + 1) * page. Rows
+        without a full page are groups of their own with prefix 0. The others
+        fall into families by the id of their page 0; a family is sorted by
+        (ids of the row's leading full pages that another row holds too, row
+        index), so rows with long common runs are neighbours, and cut into
+        groups of at most 16 / (Hq / Hkv) rows. A group's prefix is the
+        longest run of leading full pages all its members name, times the
+        page size; a group of one has prefix 0.
+
+        A full page that two rows name is never written: the first write
+        into a shared page replaces its id in the writer's list (_reserve).
+        """
+        hkv = self.k_pool.size(1)
+        hq = hkv if q_heads is None else q_heads
+        if hq <= 0 or hq % hkv or hq // hkv > 16:
+            raise ValueError(f"shared_plan: q_heads = {hq} must be a "
+                             f"multiple of Hkv = {hkv} with Hq/Hkv <= 16")
+        per = 16 // (hq // hkv)
+        full = [n // self._page for n in self.local_lens]
+        families: dict[int, list[int]] = {}
+        groups: list[tuple[list[int], int]] = []
+        for b in range(self.batch):
+            if full[b]:
+                families.setdefault(self._pages[b][0], []).append(b)
+            else:
+                groups.append(([b], 0))
+
+        def shared_run(b: int) -> list[int]:
+            run = []
+            for pid in self._pages[b][: full[b]]:
+                if self._refs[pid] < 2:
+                    break
+                run.append(pid)
+            return run
+
+        for fam in families.values():
+            fam.sort(key=lambda b: (shared_run(b), b))
+            for i in range(0, len(fam), per):
+                rows = fam[i : i + per]
+                n = 0
+                if len(rows) > 1:
+                    lead = self._pages[rows[0]]
+                    n = min(full[b] for b in rows)
+                    for b in rows[1:]:
+                        m = 0
+                        while m < n and self._pages[b][m] == lead[m]:
+                            m += 1
+                        n = m
+                groups.append((rows, n * self._page))
+        groups.sort(key=lambda g: min(g[0]))
+        return groups
+
+    def _shared_tables(self, hq: int) -> dict:
+        """The device copy of shared_plan(hq): members (B, 16) int32, counts
+        (B,) int32, prefix (B,) int64 (one entry per group, B at the most;
+        the unused groups have count 0) and start (B,) int64, each row's
+        first key outside its group's prefix. Uploaded only when the plan
+        differs from the one the buffers hold; the plan itself is recomputed
+        only after a page changed hands or a row's number of full pages
+        moved, so a steady decode step costs one tuple comparison."""
+        t = self._shared.get(hq)
+        if t is None:
+            dev, b = self.device, self.batch
+            t = self._shared[hq] = {
+                "key": None, "plan": None,
+                "members": torch.zeros(b, 16, dtype=torch.int32, device=dev),
+                "counts": torch.zeros(b, dtype=torch.int32, device=dev),
+                "prefix": torch.zeros(b, dtype=torch.long, device=dev),
+                "start": torch.zeros(b, dtype=torch.long, device=dev),
+            }
+        key = (self._page_moves,
+               tuple(n // self._page for n in self.local_lens))
+        if key == t["key"]:
+            return t
+        t["key"] = key
+        plan = self.shared_plan(hq)
+        if plan == t["plan"]:
+            return t
+        t["plan"] = plan
+        members = torch.zeros(self.batch, 16, dtype=torch.int32)
+        counts = torch.zeros(self.batch, dtype=torch.int32)
+        prefix = torch.zeros(self.batch, dtype=torch.long)
+        start = torch.zeros(self.batch, dtype=torch.long)
+        for g, (rows, n) in enumerate(plan):
+            members[g, : len(rows)] = torch.tensor(rows, dtype=torch.int32)
+            counts[g] = len(rows)
+            prefix[g] = n
+            start[rows] = n
+        for name, host in (("members", members), ("counts", counts),
+                           ("prefix", prefix), ("start", start)):
+            t[name].copy_(host)
+        self.shared_plan_uploads += 1
+        return t
+
+    def _launch_attend_shared(self, ext, q, scale: float, tables: dict):
+        return ext.flash_attention_paged_shared(
+            q.contiguous(), self.k_pool, self.v_pool, self.page_table,
+            self.local_len_dev, tables["members"], tables["counts"],
+            tables["prefix"], tables["start"], scale)
+
+    def _local_partial_shared(self, q: torch.Tensor,
+                              softmax_scale: float | None):
+        self._check_shared(q)
+        tables = self._shared_tables(q.shape[1])
+        if _zero_copy_ok(q, self._kv):
+            return self._launch_attend_shared(
+                self._ext(), q, _scale(softmax_scale, q), tables)
+        # the same two passes in torch: per group the prefix rows gathered
+        # once for all members' queries, per row the remainder, one merge
+        out_p, lse_p = _empty_partial(q)
+        out_s, lse_s = _empty_partial(q)
+        for rows, n in tables["plan"]:
+            if n:
+                k, v = self._fallback_rows(q[:1], rows[0], n)
+                o, l = local_attention(
+                    q[rows], k.expand(len(rows), -1, -1, -1),
+                    v.expand(len(rows), -1, -1, -1), softmax_scale)
+                out_p[rows], lse_p[rows] = o, l
+            for b in rows:
+                if self.local_lens[b] > n:
+                    qb = q[b : b + 1]
+                    k, v = self._fallback_rows(qb, b, self.local_lens[b])
+                    out_s[b : b + 1], lse_s[b : b + 1] = local_attention(
+                        qb, k[:, :, n:], v[:, :, n:], softmax_scale)
+        return combine_partials(torch.stack([out_p, out_s]),
+                                torch.stack([lse_p, lse_s]))
 
     def _launch_append_n(self, ext, k_new, v_new, counts_dev, vis_dev) -> None:
         ext.kv_pool_append_n(
