@@ -37,7 +37,34 @@ from __future__ import annotations
 import torch
 
 __all__ = ["quantize_k_mx", "dequantize_k_mx", "quantize_v_mx",
-           "dequantize_v_mx", "mx_group_index"]
+           "dequantize_v_mx", "mx_group_index", "quantize_rows_fp8",
+           "dequantize_rows_fp8"]
+
+_ROW_TINY = 2.0 ** -100   # amax floor: a zero row gets a finite scale
+
+
+def quantize_rows_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Per-token-scaled fp8 ("fp8_scaled"): one fp32 scale per row of the
+    last dimension, all in fp32:
+
+        scale   = max(amax(|x|), 2^-100) / 448
+        payload = e4m3(clamp(x / scale, -448, 448))   round-to-nearest-even
+
+    x (..., D) -> (payload (..., D) float8_e4m3fn, scale (...) fp32). Both
+    divisions are IEEE fp32 divisions, which kv_append_quant_kernel
+    (ops/hip/fa_kernels.hip) performs too: the kernel's bytes and scales
+    equal these bit for bit. A row of zeros gets scale 2^-100 / 448 and a
+    zero payload, so log(scale) is finite for every row."""
+    xf = x.to(torch.float32)
+    scale = xf.abs().amax(dim=-1).clamp_min(_ROW_TINY) / 448.0
+    y = (xf / scale.unsqueeze(-1)).clamp(-448.0, 448.0)
+    return y.to(torch.float8_e4m3fn), scale
+
+
+def dequantize_rows_fp8(payload: torch.Tensor,
+                        scale: torch.Tensor) -> torch.Tensor:
+    """payload (..., D) e4m3 and scale (...) fp32 -> fp32 rows."""
+    return payload.to(torch.float32) * scale.unsqueeze(-1)
 
 _E4M3_MAX = 448.0
 

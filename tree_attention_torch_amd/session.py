@@ -21,6 +21,7 @@ position block*((t // block) // world) + t % block.
 
 from __future__ import annotations
 
+import functools
 import math
 
 import torch
@@ -28,6 +29,7 @@ import torch.distributed as dist
 
 from .ops.flash import local_attention
 from .parallel.combine import combine_partials, tree_combine
+from .quant import dequantize_rows_fp8, quantize_rows_fp8
 
 __all__ = ["DecodeSession", "RaggedDecodeSession", "PagedDecodeSession"]
 
@@ -37,6 +39,20 @@ _DTYPES = {
     "fp32": torch.float32,
     "fp8": torch.float8_e4m3fn,
 }
+
+
+def _not_scaled(fn):
+    """The per-token-scaled fp8 store serves the plain decode step only:
+    the wrapped method raises under kv_dtype="fp8_scaled"."""
+    @functools.wraps(fn)
+    def guard(self, *args, **kwargs):
+        if self.scaled:
+            raise NotImplementedError(
+                f"{type(self).__name__}.{fn.__name__}: not available under "
+                "kv_dtype='fp8_scaled' (prefill, append, attend, "
+                "graphed_step and reset are)")
+        return fn(self, *args, **kwargs)
+    return guard
 
 
 def _rank_world(group) -> tuple[int, int]:
@@ -156,6 +172,10 @@ class DecodeSession:
         block: int = 256,
         group: dist.ProcessGroup | None = None,
     ) -> None:
+        if isinstance(kv_dtype, str) and kv_dtype == "fp8_scaled":
+            raise NotImplementedError(
+                "DecodeSession: kv_dtype='fp8_scaled' is served by "
+                "RaggedDecodeSession and PagedDecodeSession")
         self.device = torch.device(device)
         self.rank, self.world = _rank_world(group)
         self.group = group
@@ -452,7 +472,10 @@ class RaggedDecodeSession:
     graphed_step_many) or as a token tree (append_tree, attend_tree, commit,
     graphed_step_tree). No MX
     cache (its 64-token quantization windows are host-side state per
-    sequence).
+    sequence); the outlier-safe 1-byte store is kv_dtype="fp8_scaled": e4m3
+    with one fp32 scale per (token, KV head) row, quantized by the append
+    kernel inside the graphed step (prefill, append, attend, graphed_step and
+    reset only; head_dim 128, bf16 queries, Hq/Hkv <= 16).
 
     Where a local position lives is the subclass seam: the methods under
     "storage" below are all that PagedDecodeSession replaces.
@@ -474,6 +497,22 @@ class RaggedDecodeSession:
         self.k = torch.empty(batch, kv_heads, local_cap, head_dim, dtype=td,
                              device=self.device)
         self.v = torch.empty_like(self.k)
+        self._alloc_scales(self.k)
+
+    def _alloc_scales(self, store: torch.Tensor) -> None:
+        """fp8_scaled: one fp32 scale per stored K row and V row, shaped as
+        the store without head_dim (a page's scales live at the page's
+        index). Ones, so that a row never written still has a finite
+        positive scale."""
+        self.k_scale = self.v_scale = None
+        if self.scaled:
+            if store.size(3) != 128:
+                raise ValueError(
+                    f"{type(self).__name__}: kv_dtype='fp8_scaled' needs "
+                    f"head_dim 128, got {store.size(3)}")
+            self.k_scale = torch.ones(store.shape[:3], dtype=torch.float32,
+                                      device=self.device)
+            self.v_scale = torch.ones_like(self.k_scale)
 
     def _setup(self, batch, max_tokens, device, kv_dtype, block, group):
         """Everything but the KV storage: rank and world, the lengths on
@@ -485,6 +524,11 @@ class RaggedDecodeSession:
                 f"{name}: the MX cache keeps host-side window "
                 "state per sequence and is not supported; use bf16, fp16, "
                 "fp32 or fp8")
+        # per-token-scaled fp8: the e4m3 payload of "fp8" plus one fp32 scale
+        # per (token, KV head) row of K and of V (quant.quantize_rows_fp8)
+        self.scaled = isinstance(kv_dtype, str) and kv_dtype == "fp8_scaled"
+        if self.scaled:
+            kv_dtype = "fp8"
         if isinstance(kv_dtype, str) and kv_dtype not in _DTYPES:
             raise ValueError(f"{name}: unknown kv_dtype "
                              f"{kv_dtype!r}")
@@ -541,12 +585,24 @@ class RaggedDecodeSession:
         """Host store of (Hkv, n, D) rows of sequence b at local positions
         [pos, pos + n), cast to the storage dtype."""
         n = k_rows.shape[1]
+        if self.scaled:
+            for rows, store, scales in ((k_rows, self.k, self.k_scale),
+                                        (v_rows, self.v, self.v_scale)):
+                payload, scale = quantize_rows_fp8(rows)
+                store[b, :, pos : pos + n] = payload
+                scales[b, :, pos : pos + n] = scale
+            return
         self.k[b, :, pos : pos + n] = k_rows.to(self.k.dtype)
         self.v[b, :, pos : pos + n] = v_rows.to(self.v.dtype)
 
     def _rows(self, b: int, n: int):
         """Row b's first n local positions as contiguous (1, Hkv, n, D) K
-        and V."""
+        and V (fp8_scaled: dequantized to fp32)."""
+        if self.scaled:
+            return (dequantize_rows_fp8(self.k[b : b + 1, :, :n],
+                                        self.k_scale[b : b + 1, :, :n]),
+                    dequantize_rows_fp8(self.v[b : b + 1, :, :n],
+                                        self.v_scale[b : b + 1, :, :n]))
         return (self.k[b : b + 1, :, :n].contiguous(),
                 self.v[b : b + 1, :, :n].contiguous())
 
@@ -555,6 +611,14 @@ class RaggedDecodeSession:
         return self._rows(b, n)
 
     def _launch_append(self, ext, k_new, v_new, active_dev) -> None:
+        if self.scaled:   # one launch from bf16 rows: the kernel quantizes
+            ext.kv_cache_append_quant(
+                self.k, self.v, self.k_scale, self.v_scale,
+                k_new.to(torch.bfloat16).contiguous(),
+                v_new.to(torch.bfloat16).contiguous(), self.total_dev,
+                self.local_len_dev, active_dev, self.block, self.rank,
+                self.world)
+            return
         # the cast to the cache dtype (fp8 included) stays a torch op; the
         # kernel copies bytes
         ext.kv_cache_append(
@@ -566,6 +630,10 @@ class RaggedDecodeSession:
     def _launch_attend(self, ext, q, scale: float):
         # one launch for the whole ragged batch: every block clips its
         # chunk to its own row's length, read from local_len_dev
+        if self.scaled:
+            return ext.flash_attention_cache_scaled(
+                q.contiguous(), self.k, self.v, self.k_scale, self.v_scale,
+                self.local_len_dev, scale)
         return ext.flash_attention_cache(q.contiguous(), self.k, self.v,
                                          self.local_len_dev, scale)
 
@@ -746,6 +814,7 @@ class RaggedDecodeSession:
         self.local_lens[b] = 0
         self._push_lengths(b)
 
+    @_not_scaled
     def fork(self, src: int, dst: int, tokens: int | None = None) -> None:
         """Slot dst becomes a sequence holding the first ``tokens`` global
         tokens of sequence src (None: all of them); whatever dst held is
@@ -858,6 +927,7 @@ class RaggedDecodeSession:
             self.totals[b] = t0 + c
         self._spec = (t, vis, tuple(self.totals))
 
+    @_not_scaled
     def append_many(self, k_new: torch.Tensor, v_new: torch.Tensor,
                     counts=None) -> None:
         """Append up to T draft tokens per sequence, (B, Hkv, T, D): row b
@@ -888,6 +958,7 @@ class RaggedDecodeSession:
                                               dtype=torch.long))
         vis_dev.copy_(torch.tensor(self._spec[1], dtype=torch.long))
 
+    @_not_scaled
     def truncate(self, b: int, total: int) -> None:
         """Cut sequence b back to its first `total` tokens (the rejected
         drafts of a verify step): lengths on host and device; nothing is
@@ -971,6 +1042,7 @@ class RaggedDecodeSession:
                       "totals": tuple(self.totals),
                       "parents_dev": parents_dev, "parents": parents_host}
 
+    @_not_scaled
     def append_tree(self, k_new: torch.Tensor, v_new: torch.Tensor, parents,
                     counts=None) -> None:
         """Append up to T draft NODES of a token tree per sequence, (B, Hkv,
@@ -1073,6 +1145,7 @@ class RaggedDecodeSession:
             lses.append(torch.cat(row_l, dim=2))
         return torch.cat(outs), torch.cat(lses)
 
+    @_not_scaled
     def attend_tree(self, q: torch.Tensor, softmax_scale: float | None = None,
                     combine: str = "auto") -> torch.Tensor:
         """Verify the nodes of the last append_tree: q (B, Hq, T, D) -> (B,
@@ -1091,6 +1164,7 @@ class RaggedDecodeSession:
         out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
         return out
 
+    @_not_scaled
     def commit(self, paths, lens) -> None:
         """Keep, per sequence, the accepted root-to-node path of the last
         append_tree and drop the other drafts: nodes paths[b][:lens[b]]
@@ -1161,6 +1235,10 @@ class RaggedDecodeSession:
         if _zero_copy_ok(q, self._kv):
             return self._launch_attend(self._ext(), q,
                                        _scale(softmax_scale, q))
+        if self.scaled and q.device.type == "cuda":
+            raise ValueError(
+                f"{type(self).__name__}: kv_dtype='fp8_scaled' needs a bf16 "
+                "query and Hq/Hkv <= 16 on the GPU")
         outs, lses = [], []
         for b, n in enumerate(self.local_lens):
             qb = q[b : b + 1]
@@ -1190,6 +1268,10 @@ class RaggedDecodeSession:
         all-zero row. ``shared`` (PagedDecodeSession only): rows that hold
         the same leading full pages attend them in one KV stream per group
         (shared_plan) and their remainders on their own; same result."""
+        if shared and self.scaled:
+            raise NotImplementedError(
+                f"{type(self).__name__}.attend: shared=True is not available "
+                "under kv_dtype='fp8_scaled'")
         if shared:
             out_l, lse_l = self._local_partial_shared(q, softmax_scale)
         else:
@@ -1228,6 +1310,7 @@ class RaggedDecodeSession:
             lses.append(torch.cat(row_l, dim=2))
         return torch.cat(outs), torch.cat(lses)
 
+    @_not_scaled
     def attend_many(self, q: torch.Tensor,
                     softmax_scale: float | None = None,
                     combine: str = "auto") -> torch.Tensor:
@@ -1271,6 +1354,10 @@ class RaggedDecodeSession:
         size > 1 the local partial replays from the graph and the collective
         runs eagerly (graphed_attend).
         """
+        if shared and self.scaled:
+            raise NotImplementedError(
+                f"{type(self).__name__}.graphed_step: shared=True is not "
+                "available under kv_dtype='fp8_scaled'")
         if shared:
             self._check_shared(q_static)
         if self.device.type != "cuda":
@@ -1323,6 +1410,7 @@ class RaggedDecodeSession:
 
         return replay
 
+    @_not_scaled
     def graphed_step_many(self, q_static: torch.Tensor,
                           k_static: torch.Tensor, v_static: torch.Tensor,
                           softmax_scale: float | None = None,
@@ -1388,6 +1476,7 @@ class RaggedDecodeSession:
 
         return replay
 
+    @_not_scaled
     def graphed_step_tree(self, q_static: torch.Tensor,
                           k_static: torch.Tensor, v_static: torch.Tensor,
                           parents_static: torch.Tensor,
@@ -1523,6 +1612,7 @@ class PagedDecodeSession(RaggedDecodeSession):
         self.k_pool = torch.empty(n_pages, kv_heads, page, head_dim, dtype=td,
                                   device=self.device)
         self.v_pool = torch.empty_like(self.k_pool)
+        self._alloc_scales(self.k_pool)   # fp8_scaled: (n_pages, Hkv, page)
         # entries past a row's live pages are never read
         self.page_table = torch.zeros(batch, max_pages, dtype=torch.int32,
                                       device=self.device)
@@ -1664,6 +1754,15 @@ class PagedDecodeSession(RaggedDecodeSession):
             off = pos % self._page
             m = min(n - t, self._page - off)
             pid = self._pages[b][pos // self._page]
+            if self.scaled:
+                for rows, pool, scales in (
+                        (k_rows, self.k_pool, self.k_scale),
+                        (v_rows, self.v_pool, self.v_scale)):
+                    payload, scale = quantize_rows_fp8(rows[:, t : t + m])
+                    pool[pid, :, off : off + m] = payload
+                    scales[pid, :, off : off + m] = scale
+                t, pos = t + m, pos + m
+                continue
             self.k_pool[pid, :, off : off + m] = \
                 k_rows[:, t : t + m].to(self.k_pool.dtype)
             self.v_pool[pid, :, off : off + m] = \
@@ -1676,11 +1775,17 @@ class PagedDecodeSession(RaggedDecodeSession):
         idx = torch.tensor(self._pages[b][: (n + self._page - 1) // self._page],
                            dtype=torch.long, device=self.device)
         out = []
-        for pool in (self.k_pool, self.v_pool):
+        for pool, scales in ((self.k_pool, self.k_scale),
+                             (self.v_pool, self.v_scale)):
             pages = pool.index_select(0, idx)          # (np, Hkv, page, D)
             rows = pages.permute(1, 0, 2, 3).reshape(
                 1, pool.size(1), -1, pool.size(3))
-            out.append(rows[:, :, :n].contiguous())
+            rows = rows[:, :, :n].contiguous()
+            if self.scaled:   # the pages' scales, gathered the same way
+                sc = scales.index_select(0, idx).permute(1, 0, 2).reshape(
+                    1, pool.size(1), -1)
+                rows = dequantize_rows_fp8(rows, sc[:, :, :n])
+            out.append(rows)
         return out
 
     def _fallback_rows(self, q: torch.Tensor, b: int, n: int):
@@ -1692,6 +1797,14 @@ class PagedDecodeSession(RaggedDecodeSession):
         return k, v
 
     def _launch_append(self, ext, k_new, v_new, active_dev) -> None:
+        if self.scaled:
+            ext.kv_pool_append_quant(
+                self.k_pool, self.v_pool, self.k_scale, self.v_scale,
+                self.page_table, k_new.to(torch.bfloat16).contiguous(),
+                v_new.to(torch.bfloat16).contiguous(), self.total_dev,
+                self.local_len_dev, active_dev, self.block, self.rank,
+                self.world)
+            return
         ext.kv_pool_append(
             self.k_pool, self.v_pool, self.page_table,
             k_new.to(self.k_pool.dtype).contiguous(),
@@ -1700,6 +1813,10 @@ class PagedDecodeSession(RaggedDecodeSession):
             self.world)
 
     def _launch_attend(self, ext, q, scale: float):
+        if self.scaled:
+            return ext.flash_attention_paged_scaled(
+                q.contiguous(), self.k_pool, self.v_pool, self.k_scale,
+                self.v_scale, self.page_table, self.local_len_dev, scale)
         return ext.flash_attention_paged(
             q.contiguous(), self.k_pool, self.v_pool, self.page_table,
             self.local_len_dev, scale)
