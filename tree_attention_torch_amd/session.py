@@ -1333,6 +1333,95 @@ class RaggedDecodeSession:
         out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
         return out
 
+    # ---- chunked prefill over the cache ----
+    def _prefill_vis(self, b: int, t: int) -> torch.Tensor:
+        """(t,) int64 on the host: the local prefix each of the last t
+        tokens of row b sees, _n_local(totals[b] - t + i + 1) for all i at
+        once."""
+        seen = torch.arange(self.totals[b] - t + 1, self.totals[b] + 1,
+                            dtype=torch.long)
+        full = seen // self.block
+        return (self.block * ((full + self.world - 1 - self.rank)
+                              // self.world)
+                + torch.where(full % self.world == self.rank,
+                              seen % self.block, torch.zeros_like(seen)))
+
+    def _local_partial_prefill(self, b: int, q: torch.Tensor,
+                               vis: torch.Tensor,
+                               softmax_scale: float | None):
+        on_gpu = q.device.type == "cuda"
+        if on_gpu and self._kv.dtype == torch.float8_e4m3fn:
+            raise NotImplementedError(
+                f"{type(self).__name__}.attend_prefill: no fp8 prefill over "
+                "the cache on the GPU (kv_dtype 'fp8' and 'fp8_scaled'); use "
+                "a bf16 or fp16 store")
+        n = self.local_lens[b]
+        if n == 0:
+            return _empty_partial(q)
+        scale = _scale(softmax_scale, q)
+        if (on_gpu and q.shape[3] == 128 and self._kv.dtype == q.dtype
+                and q.dtype in (torch.bfloat16, torch.float16)):
+            return self._launch_attend_prefill(
+                self._ext(), b, q.contiguous(), scale, vis.to(self.device))
+        # eager fp32 masked softmax over the gathered rows: one matmul
+        k, v = self._rows(b, n)
+        g = q.shape[1] // k.shape[1]
+        kf = k.float().repeat_interleave(g, dim=1)
+        vf = v.float().repeat_interleave(g, dim=1)
+        s = (q.float() @ kf.transpose(-1, -2)) * scale      # (1, Hq, T, n)
+        hidden = (torch.arange(n, device=q.device)[None, :]
+                  >= vis.to(q.device)[:, None])             # (T, n)
+        s = s.masked_fill(hidden, float("-inf"))
+        m = s.amax(dim=-1, keepdim=True)
+        m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+        p = torch.exp(s - m)
+        l = p.sum(dim=-1, keepdim=True)
+        out_l = (p @ vf) / l.clamp_min(torch.finfo(torch.float32).tiny)
+        return out_l, (m + torch.log(l)).squeeze(-1)
+
+    def _launch_attend_prefill(self, ext, b: int, q, scale: float, vis_dev):
+        # the row's slab rows, cut to the tiles its live length touches: the
+        # binding plans its KV split over what it is handed
+        n = min(-(-self.local_lens[b] // 128) * 128, self.capacity)
+        return ext.flash_attention_cache_prefill(
+            q, self.k[b : b + 1, :, :n], self.v[b : b + 1, :, :n],
+            self.local_len_dev[b : b + 1], vis_dev, scale)
+
+    def attend_prefill(self, b: int, q: torch.Tensor,
+                       softmax_scale: float | None = None,
+                       combine: str = "auto") -> torch.Tensor:
+        """Chunked prefill: q (Hq, T, D) or (1, Hq, T, D) holds the queries
+        of the LAST T tokens row b holds (prefill(b, k, v) first, or fork
+        and then prefill); query i attends global positions <= totals[b] -
+        T + i, where they lie in the store -> (1, Hq, T, D) fp32. One row
+        per call, not graphed (the visible lengths go up host to device);
+        no length, page or pending draft is touched. On the GPU a bf16 /
+        fp16 store of the query's dtype with head_dim 128 runs
+        fa_prefill_cache_kernel, one KV stream per q-head; fp8 stores raise
+        NotImplementedError; anything else is an eager fp32 masked softmax
+        over the gathered rows."""
+        if not 0 <= b < self.batch:
+            raise ValueError(f"attend_prefill: b = {b} is outside "
+                             f"[0, {self.batch})")
+        if q.dim() == 3:
+            q = q[None]
+        kv = self._kv
+        if (q.dim() != 4 or q.shape[0] != 1 or q.shape[2] < 1
+                or q.shape[3] != kv.size(3) or q.shape[1] % kv.size(1)):
+            raise ValueError(
+                f"attend_prefill: q must be (Hq, T, D) or (1, Hq, T, D) with "
+                f"D = {kv.size(3)}, T >= 1 and Hq a multiple of "
+                f"{kv.size(1)}, got {tuple(q.shape)}")
+        t = q.shape[2]
+        if t > self.totals[b]:
+            raise ValueError(
+                f"attend_prefill: row {b} holds {self.totals[b]} tokens, "
+                f"fewer than the {t} queries")
+        out_l, lse_l = self._local_partial_prefill(
+            b, q, self._prefill_vis(b, t), softmax_scale)
+        out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
+        return out
+
     def graphed_step(self, q_static: torch.Tensor, k_static: torch.Tensor,
                      v_static: torch.Tensor,
                      softmax_scale: float | None = None,
@@ -1981,6 +2070,14 @@ class PagedDecodeSession(RaggedDecodeSession):
         return ext.flash_attention_paged_qlen(
             q.contiguous(), self.k_pool, self.v_pool, self.page_table,
             self.local_len_dev, vis_dev, scale)
+
+    def _launch_attend_prefill(self, ext, b: int, q, scale: float, vis_dev):
+        # the table entries of the row's live pages: the binding plans its
+        # KV split over what it is handed
+        n = -(-self.local_lens[b] // self._page)
+        return ext.flash_attention_paged_prefill(
+            q, self.k_pool, self.v_pool, self.page_table[b, :n],
+            self.local_len_dev[b : b + 1], vis_dev, scale)
 
     def _launch_append_tree(self, ext, k_new, v_new, counts_dev, parents_dev,
                             base_dev, mask_dev) -> None:
