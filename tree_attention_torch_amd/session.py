@@ -113,6 +113,16 @@ def _tree_masks(t0: int, cnt: int, parents: list[int], t: int, block: int,
     return base, masks
 
 
+def _zeroed(shape, dtype: torch.dtype, device) -> torch.Tensor:
+    """A KV store of zero bytes, in any storage dtype (fp8 included). The
+    ragged sessions start from it: rows nobody has written compare equal to
+    themselves, which the bytes a fresh allocation happens to hold (NaN
+    patterns among them) do not."""
+    t = torch.empty(tuple(shape), dtype=dtype, device=device)
+    t.view(torch.uint8).zero_()
+    return t
+
+
 def _empty_partial(q: torch.Tensor):
     """The partial of a shard that holds no key: out = 0, lse = -inf."""
     b, hq, tq, d = q.shape
@@ -494,9 +504,9 @@ class RaggedDecodeSession:
     ) -> None:
         td, local_cap = self._setup(batch, max_tokens, device, kv_dtype,
                                     block, group)
-        self.k = torch.empty(batch, kv_heads, local_cap, head_dim, dtype=td,
-                             device=self.device)
-        self.v = torch.empty_like(self.k)
+        self.k = _zeroed((batch, kv_heads, local_cap, head_dim), td,
+                         self.device)
+        self.v = _zeroed(self.k.shape, td, self.device)
         self._alloc_scales(self.k)
 
     def _alloc_scales(self, store: torch.Tensor) -> None:
@@ -1348,17 +1358,32 @@ class RaggedDecodeSession:
 
     def _local_partial_prefill(self, b: int, q: torch.Tensor,
                                vis: torch.Tensor,
-                               softmax_scale: float | None):
+                               softmax_scale: float | None,
+                               compute: str | None = None):
         on_gpu = q.device.type == "cuda"
-        if on_gpu and self._kv.dtype == torch.float8_e4m3fn:
+        fp8_store = self._kv.dtype == torch.float8_e4m3fn
+        if on_gpu and compute == "fp8":
+            for ok, what in (
+                    (fp8_store, "an 'fp8' or 'fp8_scaled' store"),
+                    (q.dtype == torch.bfloat16, "a bf16 query"),
+                    (q.shape[3] == 128, "head_dim 128")):
+                if not ok:
+                    raise ValueError(
+                        f"{type(self).__name__}.attend_prefill: "
+                        f"compute='fp8' needs {what} on the GPU")
+        elif on_gpu and fp8_store:
             raise NotImplementedError(
                 f"{type(self).__name__}.attend_prefill: no fp8 prefill over "
-                "the cache on the GPU (kv_dtype 'fp8' and 'fp8_scaled'); use "
-                "a bf16 or fp16 store")
+                "the cache on the GPU (kv_dtype 'fp8' and 'fp8_scaled') "
+                "unless compute=\"fp8\" consents to Q and P rounded to e4m3; "
+                "or use a bf16 or fp16 store")
         n = self.local_lens[b]
         if n == 0:
             return _empty_partial(q)
         scale = _scale(softmax_scale, q)
+        if on_gpu and compute == "fp8":
+            return self._launch_attend_prefill_fp8(
+                self._ext(), b, q.contiguous(), scale, vis.to(self.device))
         if (on_gpu and q.shape[3] == 128 and self._kv.dtype == q.dtype
                 and q.dtype in (torch.bfloat16, torch.float16)):
             return self._launch_attend_prefill(
@@ -1387,9 +1412,21 @@ class RaggedDecodeSession:
             q, self.k[b : b + 1, :, :n], self.v[b : b + 1, :, :n],
             self.local_len_dev[b : b + 1], vis_dev, scale)
 
+    def _launch_attend_prefill_fp8(self, ext, b: int, q, scale: float,
+                                   vis_dev):
+        # _launch_attend_prefill's cut, and the row's scale rows cut alike
+        n = min(-(-self.local_lens[b] // 128) * 128, self.capacity)
+        scales = ((self.k_scale[b : b + 1, :, :n],
+                   self.v_scale[b : b + 1, :, :n]) if self.scaled
+                  else (None, None))
+        return ext.flash_attention_cache_prefill_fp8(
+            q, self.k[b : b + 1, :, :n], self.v[b : b + 1, :, :n],
+            self.local_len_dev[b : b + 1], vis_dev, scale, 0, *scales)
+
     def attend_prefill(self, b: int, q: torch.Tensor,
                        softmax_scale: float | None = None,
-                       combine: str = "auto") -> torch.Tensor:
+                       combine: str = "auto",
+                       compute: str | None = None) -> torch.Tensor:
         """Chunked prefill: q (Hq, T, D) or (1, Hq, T, D) holds the queries
         of the LAST T tokens row b holds (prefill(b, k, v) first, or fork
         and then prefill); query i attends global positions <= totals[b] -
@@ -1399,7 +1436,15 @@ class RaggedDecodeSession:
         fp16 store of the query's dtype with head_dim 128 runs
         fa_prefill_cache_kernel, one KV stream per q-head; fp8 stores raise
         NotImplementedError; anything else is an eager fp32 masked softmax
-        over the gathered rows."""
+        over the gathered rows. ``compute="fp8"`` is the caller's consent
+        that Q and P are rounded to e4m3: on the GPU an 'fp8' or
+        'fp8_scaled' store under a bf16 query with head_dim 128 then runs
+        fa_prefill_cache_fp8_kernel on the stored bytes (anything else is a
+        ValueError); on the CPU it changes nothing."""
+        if compute not in (None, "fp8"):
+            raise ValueError(
+                f"attend_prefill: compute must be None or 'fp8', got "
+                f"{compute!r}")
         if not 0 <= b < self.batch:
             raise ValueError(f"attend_prefill: b = {b} is outside "
                              f"[0, {self.batch})")
@@ -1418,7 +1463,7 @@ class RaggedDecodeSession:
                 f"attend_prefill: row {b} holds {self.totals[b]} tokens, "
                 f"fewer than the {t} queries")
         out_l, lse_l = self._local_partial_prefill(
-            b, q, self._prefill_vis(b, t), softmax_scale)
+            b, q, self._prefill_vis(b, t), softmax_scale, compute)
         out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
         return out
 
@@ -1698,9 +1743,9 @@ class PagedDecodeSession(RaggedDecodeSession):
         self._page = page
         max_pages = (local_cap + page - 1) // page
         n_pages = max(1, (pool_tokens + page - 1) // page)
-        self.k_pool = torch.empty(n_pages, kv_heads, page, head_dim, dtype=td,
-                                  device=self.device)
-        self.v_pool = torch.empty_like(self.k_pool)
+        self.k_pool = _zeroed((n_pages, kv_heads, page, head_dim), td,
+                              self.device)
+        self.v_pool = _zeroed(self.k_pool.shape, td, self.device)
         self._alloc_scales(self.k_pool)   # fp8_scaled: (n_pages, Hkv, page)
         # entries past a row's live pages are never read
         self.page_table = torch.zeros(batch, max_pages, dtype=torch.int32,
@@ -2078,6 +2123,14 @@ class PagedDecodeSession(RaggedDecodeSession):
         return ext.flash_attention_paged_prefill(
             q, self.k_pool, self.v_pool, self.page_table[b, :n],
             self.local_len_dev[b : b + 1], vis_dev, scale)
+
+    def _launch_attend_prefill_fp8(self, ext, b: int, q, scale: float,
+                                   vis_dev):
+        n = -(-self.local_lens[b] // self._page)
+        scales = (self.k_scale, self.v_scale) if self.scaled else (None, None)
+        return ext.flash_attention_paged_prefill_fp8(
+            q, self.k_pool, self.v_pool, self.page_table[b, :n],
+            self.local_len_dev[b : b + 1], vis_dev, scale, 0, *scales)
 
     def _launch_append_tree(self, ext, k_new, v_new, counts_dev, parents_dev,
                             base_dev, mask_dev) -> None:
