@@ -15,13 +15,16 @@ Public surface (reference parity, SURVEY.md §0 capability set):
     local_attention        same, with GQA/causal/offset controls
     tree_decode            sharded decode (model.py:85-124, fixed semantics)
     tree_attention         general entry: decode + chunked causal prefill
+    mla_decode             MLA decode partial over a shared latent cache
+    tree_mla_decode        the same, sharded along the sequence
     TreeAttention          nn.Module wrapper
     TreeAttentionConfig    workload/runtime config
 """
 
 from .config import TreeAttentionConfig
 from .data import make_data
-from .ops.flash import flash_res_lse, hip_available, local_attention
+from .ops.flash import (flash_res_lse, hip_available, local_attention,
+                        mla_decode)
 from .ops.reference import attention_reference
 from .parallel.combine import (
     combine_partials,
@@ -30,7 +33,8 @@ from .parallel.combine import (
     tree_combine_allreduce,
 )
 from .parallel.pg import cleanup, is_distributed, local_device, setup
-from .parallel.tree import TreeAttention, tree_attention, tree_decode
+from .parallel.tree import (TreeAttention, tree_attention, tree_decode,
+                            tree_mla_decode)
 from .session import DecodeSession, PagedDecodeSession, RaggedDecodeSession
 from .utils.logging import logger
 
@@ -52,10 +56,12 @@ __all__ = [
     "local_device",
     "logger",
     "make_data",
+    "mla_decode",
     "setup",
     "tree_attention",
     "tree_combine",
     "tree_combine_allgather",
     "tree_combine_allreduce",
     "tree_decode",
+    "tree_mla_decode",
 ]

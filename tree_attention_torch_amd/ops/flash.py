@@ -236,6 +236,71 @@ def local_attention_mx(
     )
 
 
+MLA_D_QK = 576   # 512 latent + 64 rotary columns of a cache row
+MLA_D_V = 512    # V is the first 512 columns of the row that K is
+MLA_MAX_HEADS = 128
+
+
+def mla_decode(
+    q: torch.Tensor,
+    ckv: torch.Tensor,
+    kv_lens: torch.Tensor | None = None,
+    softmax_scale: float | None = None,
+    splits: int | None = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Multi-head latent attention decode partial over a shared latent cache.
+
+    q is (B, Hq, 1, 576) with the up-projections absorbed, ckv (B, 1, Tkv,
+    576) of the same dtype: one row per token, read by every head; K is the
+    row and V its first 512 columns. ckv may be a view along the key axis of
+    a larger preallocated buffer. kv_lens: optional (B,) int64 on q's device,
+    the live rows of each batch row (a row of length 0 gives out = 0, lse =
+    -inf). splits forces the split-KV count (None: the plan).
+
+    Returns out (B, Hq, 1, 512) fp32 and lse (B, Hq, 1) fp32: a partial that
+    combine_partials / tree_combine merge like any other.
+    """
+    if q.dim() != 4 or ckv.dim() != 4:
+        raise ValueError("mla_decode: q is (B, Hq, Tq, 576), ckv (B, 1, Tkv, 576)")
+    if q.shape[-1] != MLA_D_QK or ckv.shape[-1] != MLA_D_QK:
+        raise ValueError(
+            f"mla_decode: (d_qk, d_v) = ({MLA_D_QK}, {MLA_D_V}) is the only "
+            f"supported pair (got q width {q.shape[-1]}, ckv width "
+            f"{ckv.shape[-1]})")
+    if q.shape[2] != 1:
+        raise NotImplementedError(
+            f"mla_decode: Tq = {q.shape[2]}; only Tq = 1 (plain decode) is "
+            "implemented")
+    if ckv.shape[1] != 1 or ckv.shape[0] != q.shape[0]:
+        raise ValueError("mla_decode: ckv must be (B, 1, Tkv, 576) with q's B")
+    if q.shape[1] > MLA_MAX_HEADS:
+        raise ValueError(
+            f"mla_decode: Hq = {q.shape[1]} exceeds the native limit of "
+            f"{MLA_MAX_HEADS} heads per launch")
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(MLA_D_QK)
+    if q.device.type != "cuda":
+        return reference.mla_reference(q, ckv, kv_lens, softmax_scale)
+    ext = _load_extension()
+    if ext is None:
+        raise RuntimeError(
+            "mla_decode: the gfx950 HIP extension _tree_attn_hip is not built "
+            "but a GPU tensor was passed. Build it with "
+            f"__graft_entry__.build(). Import error: {_EXT_ERR}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or ckv.dtype != q.dtype:
+        raise ValueError("mla_decode: q and ckv must both be bf16 or both fp16")
+    b, hq = q.shape[0], q.shape[1]
+    if ckv.shape[2] == 0:  # no key at all: nothing to launch
+        return (q.new_zeros((b, hq, 1, MLA_D_V), dtype=torch.float32),
+                q.new_full((b, hq, 1), float("-inf"), dtype=torch.float32))
+    if ckv.stride(3) != 1 or ckv.stride(2) != MLA_D_QK:
+        ckv = ckv.contiguous()
+    if kv_lens is not None:
+        kv_lens = kv_lens.to(device=q.device, dtype=torch.int64).contiguous()
+    return ext.flash_attention_mla(q.contiguous(), ckv, kv_lens,
+                                   float(softmax_scale), int(splits or 0))
+
+
 # Reference-compatible alias: same name/signature shape as model.py:60.
 def flash_res_lse(
     q: torch.Tensor,
@@ -248,4 +313,4 @@ def flash_res_lse(
 
 
 __all__ = ["local_attention", "local_attention_mx", "flash_res_lse",
-           "hip_available", "decode_loop_chunks"]
+           "hip_available", "decode_loop_chunks", "mla_decode"]

@@ -23,7 +23,8 @@ import math
 
 import torch
 
-__all__ = ["flash_res_lse", "attention_reference", "repeat_kv"]
+__all__ = ["flash_res_lse", "attention_reference", "repeat_kv",
+           "mla_reference"]
 
 
 def repeat_kv(x: torch.Tensor, n_rep: int) -> torch.Tensor:
@@ -105,3 +106,37 @@ def attention_reference(
     sharded == unsharded tests."""
     out, _ = flash_res_lse(q, k, v, softmax_scale=softmax_scale, is_causal=is_causal)
     return out
+
+
+def mla_reference(
+    q: torch.Tensor,
+    ckv: torch.Tensor,
+    kv_lens: torch.Tensor | None = None,
+    softmax_scale: float | None = None,
+    d_v: int = 512,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """fp32 oracle of the MLA decode partial (ops/flash.py::mla_decode).
+
+    q (B, Hq, Tq, d_qk) against the shared latent cache ckv (B, 1, Tkv, d_qk):
+    K is the row, V its first d_v columns. kv_lens (B,) masks the keys at or
+    past each batch row's length (they may hold anything, NaN included).
+    Returns out (B, Hq, Tq, d_v) and lse (B, Hq, Tq); a row with no key has
+    out = 0 and lse = -inf.
+    """
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(q.shape[-1])
+    kf = ckv.float()
+    if kv_lens is not None:
+        pos = torch.arange(ckv.shape[2], device=ckv.device)
+        dead = pos[None, :] >= kv_lens.to(ckv.device)[:, None]  # (B, Tkv)
+        kf = kf.masked_fill(dead[:, None, :, None], 0.0)
+    scores = torch.matmul(q.float(), kf.transpose(-2, -1)) * softmax_scale
+    if kv_lens is not None:
+        scores = scores.masked_fill(dead[:, None, None, :], float("-inf"))
+    lse = torch.logsumexp(scores, dim=-1)
+    m = scores.amax(dim=-1, keepdim=True)
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    p = torch.exp(scores - m)
+    denom = p.sum(dim=-1, keepdim=True)
+    denom = torch.where(denom == 0, torch.ones_like(denom), denom)
+    return torch.matmul(p / denom, kf[..., :d_v]), lse

@@ -21,10 +21,11 @@ import math
 import torch
 import torch.distributed as dist
 
-from ..ops.flash import local_attention
+from ..ops.flash import local_attention, mla_decode
 from .combine import tree_combine
 
-__all__ = ["tree_decode", "tree_attention", "TreeAttention"]
+__all__ = ["tree_decode", "tree_attention", "tree_mla_decode",
+           "TreeAttention"]
 
 
 def default_q_chunk(tq: int, b: int, hq: int) -> int:
@@ -176,6 +177,26 @@ def tree_decode(
     derived from the process group when omitted."""
     del rank, world_size, device  # derived from the process group
     return tree_attention(q, k, v, softmax_scale=softmax_scale, combine=combine)
+
+
+def tree_mla_decode(
+    q: torch.Tensor,
+    ckv_shard: torch.Tensor,
+    kv_lens: torch.Tensor | None = None,
+    softmax_scale: float | None = None,
+    combine: str = "auto",
+    group: dist.ProcessGroup | None = None,
+) -> torch.Tensor:
+    """MLA decode over a latent cache sharded along the sequence: q (B, Hq, 1,
+    576) is replicated, ckv_shard (B, 1, T_local, 576) is THIS rank's rows and
+    kv_lens (B,) its live lengths. The local partial (ops/flash.py::
+    mla_decode) goes through tree_combine as any other; at width 512 the
+    all-gather branch reduces with the eager combine_partials, the all-reduce
+    branch with the width-generic rescale / finish kernels.
+    Returns out (B, Hq, 1, 512) fp32."""
+    out_l, lse_l = mla_decode(q, ckv_shard, kv_lens, softmax_scale)
+    out, _ = tree_combine(out_l, lse_l, strategy=combine, group=group)
+    return out
 
 
 class TreeAttention(torch.nn.Module):
