@@ -17,6 +17,9 @@ Public surface (reference parity, SURVEY.md §0 capability set):
     tree_attention         general entry: decode + chunked causal prefill
     mla_decode             MLA decode partial over a shared latent cache
     tree_mla_decode        the same, sharded along the sequence
+    mla_decode_paged       the same partial over a paged latent pool, with
+                           up to 16 query positions per row
+    PagedMlaSession        the MLA serving loop over that pool
     TreeAttention          nn.Module wrapper
     TreeAttentionConfig    workload/runtime config
 """
@@ -24,7 +27,7 @@ Public surface (reference parity, SURVEY.md §0 capability set):
 from .config import TreeAttentionConfig
 from .data import make_data
 from .ops.flash import (flash_res_lse, hip_available, local_attention,
-                        mla_decode)
+                        mla_decode, mla_decode_paged)
 from .ops.reference import attention_reference
 from .parallel.combine import (
     combine_partials,
@@ -35,7 +38,8 @@ from .parallel.combine import (
 from .parallel.pg import cleanup, is_distributed, local_device, setup
 from .parallel.tree import (TreeAttention, tree_attention, tree_decode,
                             tree_mla_decode)
-from .session import DecodeSession, PagedDecodeSession, RaggedDecodeSession
+from .session import (DecodeSession, PagedDecodeSession, PagedMlaSession,
+                      RaggedDecodeSession)
 from .utils.logging import logger
 
 __version__ = "0.1.0"
@@ -43,6 +47,7 @@ __version__ = "0.1.0"
 __all__ = [
     "DecodeSession",
     "PagedDecodeSession",
+    "PagedMlaSession",
     "RaggedDecodeSession",
     "TreeAttention",
     "TreeAttentionConfig",
@@ -57,6 +62,7 @@ __all__ = [
     "logger",
     "make_data",
     "mla_decode",
+    "mla_decode_paged",
     "setup",
     "tree_attention",
     "tree_combine",

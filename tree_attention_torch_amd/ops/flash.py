@@ -301,6 +301,96 @@ def mla_decode(
                                    float(softmax_scale), int(splits or 0))
 
 
+MLA_PAGE_SIZES = (128, 256, 512, 1024)
+MLA_MAX_TQ = 16
+
+
+def mla_chain_vis(kv_lens: torch.Tensor, tq: int) -> torch.Tensor:
+    """The chain mask of a verify step whose tq drafts are the last tq rows
+    of each sequence: vis[b, i] = max(kv_lens[b] - (tq - 1 - i), 0)."""
+    back = torch.arange(tq - 1, -1, -1, device=kv_lens.device)
+    return (kv_lens.to(torch.int64)[:, None] - back[None, :]).clamp(min=0)
+
+
+def mla_decode_paged(
+    q: torch.Tensor,
+    pool: torch.Tensor,
+    page_table: torch.Tensor,
+    kv_lens: torch.Tensor,
+    vis: torch.Tensor | None = None,
+    softmax_scale: float | None = None,
+    splits: int = 0,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """MLA decode partial over a PAGED latent pool, Tq query positions per
+    row (a multi-token verify step).
+
+    q is (B, Hq, Tq, 576) with Tq in 1..16, pool (n_pages, 1, page, 576) of
+    q's dtype with page in 128 / 256 / 512 / 1024, page_table (B, max_pages)
+    int32: entry [b, j] is the page of row b's positions [j * page, (j + 1) *
+    page), clamped into the pool; only entries j < ceil(kv_lens[b] / page)
+    are read. kv_lens (B,) is each row's length (at most max_pages * page).
+    vis (B, Tq) int64: query position i of row b sees the keys below
+    min(vis[b, i], kv_lens[b]); None is the chain mask mla_chain_vis. splits
+    forces the split-KV count (0: the plan).
+
+    Returns out (B, Hq, Tq, 512) fp32 and lse (B, Hq, Tq) fp32; a query that
+    sees no key has out = 0 and lse = -inf.
+    """
+    who = "mla_decode_paged"
+    if q.dim() != 4 or q.shape[-1] != MLA_D_QK:
+        raise ValueError(f"{who}: q is (B, Hq, Tq, {MLA_D_QK})")
+    b, hq, tq = q.shape[:3]
+    if not 1 <= tq <= MLA_MAX_TQ:
+        raise ValueError(f"{who}: Tq = {tq} is outside 1..{MLA_MAX_TQ}")
+    if not 1 <= hq <= MLA_MAX_HEADS:
+        raise ValueError(
+            f"{who}: Hq = {hq} is outside the native range 1..{MLA_MAX_HEADS}")
+    if (pool.dim() != 4 or pool.shape[1] != 1 or pool.shape[3] != MLA_D_QK
+            or pool.shape[0] < 1):
+        raise ValueError(f"{who}: pool is (n_pages, 1, page, {MLA_D_QK})")
+    page = pool.shape[2]
+    if page not in MLA_PAGE_SIZES:
+        raise ValueError(f"{who}: page must be one of {MLA_PAGE_SIZES}, got "
+                         f"{page}")
+    if pool.dtype != q.dtype:
+        raise ValueError(f"{who}: q and pool must have one dtype")
+    if (page_table.dim() != 2 or page_table.shape[0] != b
+            or page_table.shape[1] < 1 or page_table.dtype != torch.int32):
+        raise ValueError(f"{who}: page_table is int32 (B, max_pages)")
+    if kv_lens.dim() != 1 or kv_lens.shape[0] != b:
+        raise ValueError(f"{who}: kv_lens is (B,)")
+    if vis is not None and tuple(vis.shape) != (b, tq):
+        raise ValueError(f"{who}: vis is (B, Tq) = ({b}, {tq}), got "
+                         f"{tuple(vis.shape)}")
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(MLA_D_QK)
+    kv_lens = kv_lens.to(device=q.device, dtype=torch.int64).contiguous()
+    if vis is None:
+        vis = mla_chain_vis(kv_lens, tq) if tq > 1 else None
+    else:
+        vis = vis.to(device=q.device, dtype=torch.int64).contiguous()
+    if q.device.type != "cuda":
+        cap = page_table.shape[1] * page
+        lens = kv_lens.clamp(0, cap)
+        n_max = int(lens.max())
+        ckv = pool.new_zeros((b, 1, max(n_max, 1), MLA_D_QK))
+        for i, n in enumerate(lens.tolist()):
+            ids = page_table[i, : -(-n // page)].long().clamp(0, pool.shape[0] - 1)
+            ckv[i, 0, :n] = pool[ids, 0].reshape(-1, MLA_D_QK)[:n]
+        return reference.mla_reference(q, ckv, lens, softmax_scale, vis=vis)
+    ext = _load_extension()
+    if ext is None:
+        raise RuntimeError(
+            f"{who}: the gfx950 HIP extension _tree_attn_hip is not built "
+            "but a GPU tensor was passed. Build it with "
+            f"__graft_entry__.build(). Import error: {_EXT_ERR}")
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{who}: q and pool must both be bf16 or both fp16")
+    return ext.flash_attention_mla_paged(
+        q.contiguous(), pool, page_table, kv_lens, vis, float(softmax_scale),
+        int(splits or 0))
+
+
 # Reference-compatible alias: same name/signature shape as model.py:60.
 def flash_res_lse(
     q: torch.Tensor,
@@ -313,4 +403,5 @@ def flash_res_lse(
 
 
 __all__ = ["local_attention", "local_attention_mx", "flash_res_lse",
-           "hip_available", "decode_loop_chunks", "mla_decode"]
+           "hip_available", "decode_loop_chunks", "mla_decode",
+           "mla_decode_paged", "mla_chain_vis"]

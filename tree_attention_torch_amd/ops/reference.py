@@ -114,12 +114,15 @@ def mla_reference(
     kv_lens: torch.Tensor | None = None,
     softmax_scale: float | None = None,
     d_v: int = 512,
+    vis: torch.Tensor | None = None,
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """fp32 oracle of the MLA decode partial (ops/flash.py::mla_decode).
 
     q (B, Hq, Tq, d_qk) against the shared latent cache ckv (B, 1, Tkv, d_qk):
     K is the row, V its first d_v columns. kv_lens (B,) masks the keys at or
     past each batch row's length (they may hold anything, NaN included).
+    vis (B, Tq) masks, for query position t of row b, the keys at or past
+    vis[b, t] as well (the verify step's per-query-row visible lengths).
     Returns out (B, Hq, Tq, d_v) and lse (B, Hq, Tq); a row with no key has
     out = 0 and lse = -inf.
     """
@@ -133,6 +136,10 @@ def mla_reference(
     scores = torch.matmul(q.float(), kf.transpose(-2, -1)) * softmax_scale
     if kv_lens is not None:
         scores = scores.masked_fill(dead[:, None, None, :], float("-inf"))
+    if vis is not None:
+        pos = torch.arange(ckv.shape[2], device=ckv.device)
+        unseen = pos[None, None, :] >= vis.to(ckv.device)[:, :, None]
+        scores = scores.masked_fill(unseen[:, None], float("-inf"))
     lse = torch.logsumexp(scores, dim=-1)
     m = scores.amax(dim=-1, keepdim=True)
     m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))

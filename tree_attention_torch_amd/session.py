@@ -31,7 +31,8 @@ from .ops.flash import local_attention
 from .parallel.combine import combine_partials, tree_combine
 from .quant import dequantize_rows_fp8, quantize_rows_fp8
 
-__all__ = ["DecodeSession", "RaggedDecodeSession", "PagedDecodeSession"]
+__all__ = ["DecodeSession", "RaggedDecodeSession", "PagedDecodeSession",
+           "PagedMlaSession"]
 
 _DTYPES = {
     "bf16": torch.bfloat16,
@@ -2167,3 +2168,231 @@ class PagedDecodeSession(RaggedDecodeSession):
         super().reset(b)
         self._drop(self._pages[b])
         self._pages[b] = []
+
+
+def _mla_unsupported(what: str):
+    def refuse(self, *args, **kwargs):
+        raise NotImplementedError(
+            f"PagedMlaSession: {what} is not implemented for the MLA latent "
+            "pool (prefill, append, attend, append_many, attend_many, "
+            "truncate, reset and graphed_step are)")
+    return refuse
+
+
+class PagedMlaSession(PagedDecodeSession):
+    """The serving loop of multi-head latent attention (absorbed queries)
+    over a paged latent pool: PagedDecodeSession's page bookkeeping, block-
+    cyclic sharding and host / device lengths, with ONE 576-wide latent row
+    per token that every query head reads (K is the row, V its first 512
+    columns).
+
+    ``pool`` is (n_pages, 1, page, 576) in bf16 or fp16 and ``page_table``
+    (B, max_pages) int32 on the device (ops/hip/ta_abi.h
+    ta_fa_mla_decode_paged). ``max_tokens`` is the per-sequence ceiling and
+    fixes the table's width; ``n_pages`` sizes this rank's pool for all
+    sequences together (None: every row can reach its ceiling).
+
+    attend() takes q (B, Hq, 1, 576) -> (B, Hq, 1, 512). The verify step
+    (the multi-token-prediction heads of the models that use MLA) is
+    append_many / attend_many / truncate with up to 16 drafts per row; the
+    drafts share the latent rows, so they are more MFMA rows of the same KV
+    stream. graphed_step() captures append kernel, decode kernel and split
+    combine. Not implemented: fork, tree drafts, shared-prefix decode,
+    attend_prefill, an fp8 latent store and graphed_step_many.
+    """
+
+    def __init__(
+        self,
+        batch: int,
+        max_tokens: int,
+        page: int = 128,
+        n_pages: int | None = None,
+        dtype: str | torch.dtype = "bf16",
+        block: int = 256,
+        group: dist.ProcessGroup | None = None,
+        device: torch.device | str = "cuda",
+    ) -> None:
+        from .ops.flash import MLA_D_QK
+
+        if page not in _PAGE_SIZES:
+            raise ValueError(f"PagedMlaSession: page must be one of "
+                             f"{_PAGE_SIZES}, got {page!r}")
+        td = _DTYPES.get(dtype, dtype) if isinstance(dtype, str) else dtype
+        if td == torch.float8_e4m3fn or dtype == "fp8_scaled":
+            raise NotImplementedError(
+                "PagedMlaSession: an fp8 latent store is not implemented; "
+                "use bf16 or fp16")
+        if td not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"PagedMlaSession: dtype must be bf16 or fp16, "
+                             f"got {dtype!r}")
+        _, local_cap = self._setup(batch, max_tokens, device, td, block, group)
+        self._page = page
+        max_pages = (local_cap + page - 1) // page
+        if n_pages is None:
+            n_pages = batch * max_pages
+        self.pool = _zeroed((max(1, n_pages), 1, page, MLA_D_QK), td,
+                            self.device)
+        # one payload: the parent's K / V bookkeeping sees the same tensor
+        self.k_pool = self.v_pool = self.pool
+        self._alloc_scales(self.pool)
+        self.page_table = torch.zeros(batch, max_pages, dtype=torch.int32,
+                                      device=self.device)
+        self._pages = [[] for _ in range(batch)]
+        self._free = list(range(self.pool.size(0) - 1, -1, -1))
+        self._refs = [0] * self.pool.size(0)   # never above 1: no fork
+        self._page_moves = 0
+
+    # ---- storage: one latent row per token ----
+    def _store(self, b: int, pos: int, k_rows: torch.Tensor,
+               v_rows: torch.Tensor) -> None:
+        t, n = 0, k_rows.shape[1]
+        while t < n:   # page by page; _reserve has assigned every page
+            off = pos % self._page
+            m = min(n - t, self._page - off)
+            pid = self._pages[b][pos // self._page]
+            self.pool[pid, :, off : off + m] = \
+                k_rows[:, t : t + m].to(self.pool.dtype)
+            t, pos = t + m, pos + m
+
+    def _launch_append_n(self, ext, k_new, v_new, counts_dev, vis_dev) -> None:
+        ext.mla_pool_append(
+            self.pool, self.page_table,
+            k_new.to(self.pool.dtype).contiguous(), self.total_dev,
+            self.local_len_dev, counts_dev, vis_dev, self.block, self.rank,
+            self.world)
+
+    # ---- cache updates ----
+    def _latent(self, c: torch.Tensor, who: str) -> torch.Tensor:
+        if c.dim() != 4 or c.shape[0] != self.batch or c.shape[1] != 1 \
+                or c.shape[3] != self.pool.size(3):
+            raise ValueError(
+                f"{who}: the new rows must be (B, 1, T, 576) with B = "
+                f"{self.batch}, got {tuple(c.shape)}")
+        return c
+
+    def prefill(self, b: int, c_seq: torch.Tensor) -> None:
+        """Bulk-load the latent rows of sequence b, (T, 576) or (1, T, 576)
+        or (1, 1, T, 576), behind what it already holds."""
+        c_seq = c_seq.reshape(1, -1, c_seq.shape[-1])
+        super().prefill(b, c_seq, c_seq)
+
+    def append(self, c_new: torch.Tensor, active=None) -> None:
+        """Append one latent row (B, 1, 1, 576) to every ACTIVE sequence:
+        one launch of the append kernel, a masked row taking 0 rows."""
+        c_new = self._latent(c_new, "append")
+        if c_new.shape[2] != 1:
+            raise ValueError("append: one row per sequence; append_many "
+                             "takes up to 16")
+        self.append_many(c_new, [int(on) for on in self._mask(active)])
+
+    def append_many(self, c_new: torch.Tensor, counts=None) -> None:
+        """Append up to T draft rows per sequence, (B, 1, T, 576): row b
+        takes its first counts[b]. attend_many() then verifies the drafts
+        and truncate() takes the rejected ones back out."""
+        c_new = self._latent(c_new, "append_many")
+        super().append_many(c_new, c_new, counts)
+
+    # ---- attention ----
+    def _partial(self, q: torch.Tensor, vis, softmax_scale: float | None):
+        from .ops.flash import mla_decode_paged
+
+        return mla_decode_paged(q, self.pool, self.page_table,
+                                self.local_len_dev, vis, softmax_scale)
+
+    def attend(self, q: torch.Tensor, softmax_scale: float | None = None,
+               combine: str = "auto") -> torch.Tensor:
+        """q (B, Hq, 1, 576), row b over sequence b's latent rows -> (B, Hq,
+        1, 512). A sequence that holds no token yields an all-zero row."""
+        if q.dim() != 4 or q.shape[0] != self.batch or q.shape[2] != 1:
+            raise ValueError(
+                f"attend: q must be (B, Hq, 1, 576) with B = {self.batch}, "
+                f"got {tuple(q.shape)}; attend_many takes Tq > 1")
+        out_l, lse_l = self._partial(q, None, softmax_scale)
+        out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
+        return out
+
+    def attend_many(self, q: torch.Tensor,
+                    softmax_scale: float | None = None,
+                    combine: str = "auto") -> torch.Tensor:
+        """Verify the drafts of the last append_many: q (B, Hq, T, 576) ->
+        (B, Hq, T, 512); query i of sequence b sees what it held before that
+        append plus drafts 0..min(i, counts[b] - 1)."""
+        spec = self._spec
+        if spec is None or spec[2] != tuple(self.totals):
+            raise RuntimeError(
+                "attend_many: no append_many since the lengths last moved")
+        t = spec[0]
+        if q.dim() != 4 or q.shape[0] != self.batch or q.shape[2] != t:
+            raise ValueError(
+                f"attend_many: q must be (B, Hq, T, 576) with B = "
+                f"{self.batch} and the T = {t} of the last append_many, got "
+                f"{tuple(q.shape)}")
+        out_l, lse_l = self._partial(q, self._vis_dev(t), softmax_scale)
+        out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
+        return out
+
+    def graphed_step(self, q_static: torch.Tensor, c_static: torch.Tensor,
+                     softmax_scale: float | None = None,
+                     combine: str = "auto"):
+        """Capture one decode step (append kernel, paged MLA decode kernel,
+        split combine: one linear chain) into a hipGraph. Returns ``replay``.
+
+        Write the step's query (B, Hq, 1, 576) and latent rows (B, 1, 1,
+        576) into the static tensors, then ``replay(active=None)`` checks
+        capacity on the host mirror, assigns the pages the step will touch
+        (eagerly: the page table is a static buffer the replay reads),
+        advances the mirror, refreshes the static counts and replays."""
+        if self.device.type != "cuda":
+            raise ValueError("graphed_step needs a GPU session")
+        c_static = self._latent(c_static, "graphed_step")
+        if (q_static.dim() != 4 or q_static.shape[2] != 1
+                or c_static.shape[2] != 1 or c_static.dtype != self.pool.dtype
+                or not c_static.is_contiguous()):
+            raise ValueError(
+                "graphed_step: q_static is (B, Hq, 1, 576) and c_static a "
+                "contiguous (B, 1, 1, 576) tensor of the pool's dtype")
+        ext = self._ext()
+        counts_dev = torch.zeros(self.batch, dtype=torch.int32,
+                                 device=self.device)
+        vis_dev = self._vis_dev(1)
+        scale = float(softmax_scale if softmax_scale is not None
+                      else 1.0 / math.sqrt(q_static.shape[-1]))
+
+        def step():
+            ext.mla_pool_append(self.pool, self.page_table, c_static,
+                                self.total_dev, self.local_len_dev,
+                                counts_dev, vis_dev, self.block, self.rank,
+                                self.world)
+            return ext.flash_attention_mla_paged(
+                q_static, self.pool, self.page_table, self.local_len_dev,
+                None, scale, 0)
+
+        # the warm-up runs under all-zero counts, so no length moves
+        graph, (out_l, lse_l) = _capture(step)
+        self._graph = graph  # keep alive
+        in_buffer = [[0] * self.batch]   # what counts_dev holds now
+
+        def replay(active=None) -> torch.Tensor:
+            counts = [int(on) for on in self._mask(active)]
+            self._reserve(self._many_ends(counts))
+            self._advance_many(counts, 1)
+            if counts != in_buffer[0]:
+                counts_dev.copy_(self._counts_dev(counts))
+                in_buffer[0] = counts
+            graph.replay()
+            if self.world == 1:
+                return out_l
+            out, _ = tree_combine(out_l, lse_l, strategy=combine,
+                                  group=self.group)
+            return out
+
+        return replay
+
+    fork = _mla_unsupported("fork")
+    append_tree = _mla_unsupported("append_tree (tree drafts)")
+    attend_tree = _mla_unsupported("attend_tree (tree drafts)")
+    commit = _mla_unsupported("commit (tree drafts)")
+    graphed_step_tree = _mla_unsupported("graphed_step_tree (tree drafts)")
+    graphed_step_many = _mla_unsupported("graphed_step_many")
+    attend_prefill = _mla_unsupported("attend_prefill")
+    shared_plan = _mla_unsupported("shared-prefix decode (shared_plan)")
