@@ -20,6 +20,7 @@ import os
 import torch
 
 from . import reference
+from ..quant import MLA_FP8_ROW, dequantize_mla_fp8
 
 _EXT = None
 _EXT_ERR: Exception | None = None
@@ -325,7 +326,10 @@ def mla_decode_paged(
     row (a multi-token verify step).
 
     q is (B, Hq, Tq, 576) with Tq in 1..16, pool (n_pages, 1, page, 576) of
-    q's dtype with page in 128 / 256 / 512 / 1024, page_table (B, max_pages)
+    q's dtype, or the "fp8_block" store (n_pages, 1, page, 656) uint8 of
+    quant.quantize_mla_fp8 under a bf16 q (656 B per token instead of 1152;
+    K and V are read exactly, the block scales go onto the fp32 scores and
+    onto P), with page in 128 / 256 / 512 / 1024, page_table (B, max_pages)
     int32: entry [b, j] is the page of row b's positions [j * page, (j + 1) *
     page), clamped into the pool; only entries j < ceil(kv_lens[b] / page)
     are read. kv_lens (B,) is each row's length (at most max_pages * page).
@@ -345,14 +349,20 @@ def mla_decode_paged(
     if not 1 <= hq <= MLA_MAX_HEADS:
         raise ValueError(
             f"{who}: Hq = {hq} is outside the native range 1..{MLA_MAX_HEADS}")
-    if (pool.dim() != 4 or pool.shape[1] != 1 or pool.shape[3] != MLA_D_QK
-            or pool.shape[0] < 1):
-        raise ValueError(f"{who}: pool is (n_pages, 1, page, {MLA_D_QK})")
+    fp8 = pool.dtype == torch.uint8
+    if (pool.dim() != 4 or pool.shape[1] != 1 or pool.shape[0] < 1
+            or pool.shape[3] != (MLA_FP8_ROW if fp8 else MLA_D_QK)):
+        raise ValueError(f"{who}: pool is (n_pages, 1, page, {MLA_D_QK}), or "
+                         f"(n_pages, 1, page, {MLA_FP8_ROW}) uint8")
     page = pool.shape[2]
     if page not in MLA_PAGE_SIZES:
         raise ValueError(f"{who}: page must be one of {MLA_PAGE_SIZES}, got "
                          f"{page}")
-    if pool.dtype != q.dtype:
+    if fp8 and q.dtype != torch.bfloat16:
+        raise NotImplementedError(
+            f"{who}: the fp8_block pool keeps its rotary columns in bf16 and "
+            f"takes a bf16 q (got {q.dtype})")
+    if not fp8 and pool.dtype != q.dtype:
         raise ValueError(f"{who}: q and pool must have one dtype")
     if (page_table.dim() != 2 or page_table.shape[0] != b
             or page_table.shape[1] < 1 or page_table.dtype != torch.int32):
@@ -373,17 +383,24 @@ def mla_decode_paged(
         cap = page_table.shape[1] * page
         lens = kv_lens.clamp(0, cap)
         n_max = int(lens.max())
-        ckv = pool.new_zeros((b, 1, max(n_max, 1), MLA_D_QK))
+        ckv = torch.zeros((b, 1, max(n_max, 1), MLA_D_QK),
+                          dtype=torch.float32 if fp8 else pool.dtype)
         for i, n in enumerate(lens.tolist()):
             ids = page_table[i, : -(-n // page)].long().clamp(0, pool.shape[0] - 1)
-            ckv[i, 0, :n] = pool[ids, 0].reshape(-1, MLA_D_QK)[:n]
-        return reference.mla_reference(q, ckv, lens, softmax_scale, vis=vis)
+            rows = pool[ids, 0].reshape(-1, pool.shape[3])[:n]
+            ckv[i, 0, :n] = dequantize_mla_fp8(rows) if fp8 else rows
+        return reference.mla_reference(q.float() if fp8 else q, ckv, lens,
+                                       softmax_scale, vis=vis)
     ext = _load_extension()
     if ext is None:
         raise RuntimeError(
             f"{who}: the gfx950 HIP extension _tree_attn_hip is not built "
             "but a GPU tensor was passed. Build it with "
             f"__graft_entry__.build(). Import error: {_EXT_ERR}")
+    if fp8:
+        return ext.flash_attention_mla_paged_fp8(
+            q.contiguous(), pool, page_table, kv_lens, vis,
+            float(softmax_scale), int(splits or 0))
     if q.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(f"{who}: q and pool must both be bf16 or both fp16")
     return ext.flash_attention_mla_paged(
@@ -404,4 +421,4 @@ def flash_res_lse(
 
 __all__ = ["local_attention", "local_attention_mx", "flash_res_lse",
            "hip_available", "decode_loop_chunks", "mla_decode",
-           "mla_decode_paged", "mla_chain_vis"]
+           "mla_decode_paged", "mla_chain_vis", "MLA_FP8_ROW"]

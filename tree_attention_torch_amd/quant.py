@@ -38,7 +38,8 @@ import torch
 
 __all__ = ["quantize_k_mx", "dequantize_k_mx", "quantize_v_mx",
            "dequantize_v_mx", "mx_group_index", "quantize_rows_fp8",
-           "dequantize_rows_fp8"]
+           "dequantize_rows_fp8", "quantize_mla_fp8", "dequantize_mla_fp8",
+           "MLA_FP8_ROW"]
 
 _ROW_TINY = 2.0 ** -100   # amax floor: a zero row gets a finite scale
 
@@ -65,6 +66,41 @@ def dequantize_rows_fp8(payload: torch.Tensor,
                         scale: torch.Tensor) -> torch.Tensor:
     """payload (..., D) e4m3 and scale (...) fp32 -> fp32 rows."""
     return payload.to(torch.float32) * scale.unsqueeze(-1)
+
+MLA_FP8_ROW = 656   # bytes of one "fp8_block" latent row
+_MLA_LATENT, _MLA_BLOCK = 512, 128
+
+
+def quantize_mla_fp8(c: torch.Tensor) -> torch.Tensor:
+    """The "fp8_block" MLA latent row: c (..., 576) -> (..., 656) uint8,
+
+        [0, 512)    e4m3 payload of latent columns 0..511
+        [512, 528)  four fp32 scales, one per block of 128 columns
+        [528, 656)  rotary columns 512..575 as bf16, unquantized
+
+    Each 128-column block is quantized on its own by quantize_rows_fp8's
+    rule, so mla_append_quant_kernel (ops/hip/fa_kernels.hip) writes these
+    bytes bit for bit."""
+    lead = c.shape[:-1]
+    payload, scale = quantize_rows_fp8(
+        c[..., :_MLA_LATENT].reshape(*lead, 4, _MLA_BLOCK))
+    rope = c[..., _MLA_LATENT:].to(torch.bfloat16).contiguous()
+    return torch.cat([payload.view(torch.uint8).reshape(*lead, _MLA_LATENT),
+                      scale.contiguous().view(torch.uint8).reshape(*lead, 16),
+                      rope.view(torch.uint8).reshape(*lead, 128)], dim=-1)
+
+
+def dequantize_mla_fp8(rows: torch.Tensor) -> torch.Tensor:
+    """rows (..., 656) uint8 -> the (..., 576) fp32 rows they stand for."""
+    lead = rows.shape[:-1]
+    payload = rows[..., :_MLA_LATENT].contiguous().view(torch.float8_e4m3fn)
+    scale = rows[..., _MLA_LATENT:_MLA_LATENT + 16].contiguous().view(
+        torch.float32)
+    latent = dequantize_rows_fp8(payload.reshape(*lead, 4, _MLA_BLOCK), scale)
+    rope = rows[..., _MLA_LATENT + 16:].contiguous().view(torch.bfloat16)
+    return torch.cat([latent.reshape(*lead, _MLA_LATENT), rope.float()],
+                     dim=-1)
+
 
 _E4M3_MAX = 448.0
 

@@ -29,7 +29,7 @@ import torch.distributed as dist
 
 from .ops.flash import local_attention
 from .parallel.combine import combine_partials, tree_combine
-from .quant import dequantize_rows_fp8, quantize_rows_fp8
+from .quant import dequantize_rows_fp8, quantize_mla_fp8, quantize_rows_fp8
 
 __all__ = ["DecodeSession", "RaggedDecodeSession", "PagedDecodeSession",
            "PagedMlaSession"]
@@ -2188,7 +2188,13 @@ class PagedMlaSession(PagedDecodeSession):
 
     ``pool`` is (n_pages, 1, page, 576) in bf16 or fp16 and ``page_table``
     (B, max_pages) int32 on the device (ops/hip/ta_abi.h
-    ta_fa_mla_decode_paged). ``max_tokens`` is the per-sequence ceiling and
+    ta_fa_mla_decode_paged). ``dtype="fp8_block"`` stores 656 bytes per token
+    instead of 1152 (quant.quantize_mla_fp8: the 512 latent columns as e4m3
+    with one fp32 scale per 128 columns, the 64 rotary columns in bf16), so a
+    pool of the same bytes holds 1.76x the tokens: the pool is (n_pages, 1,
+    page, 656) uint8, the caller keeps passing bf16 (.., 576) rows and bf16
+    queries, prefill quantizes on the host and the append kernel on the
+    device. ``max_tokens`` is the per-sequence ceiling and
     fixes the table's width; ``n_pages`` sizes this rank's pool for all
     sequences together (None: every row can reach its ceiling).
 
@@ -2198,7 +2204,8 @@ class PagedMlaSession(PagedDecodeSession):
     drafts share the latent rows, so they are more MFMA rows of the same KV
     stream. graphed_step() captures append kernel, decode kernel and split
     combine. Not implemented: fork, tree drafts, shared-prefix decode,
-    attend_prefill, an fp8 latent store and graphed_step_many.
+    attend_prefill, graphed_step_many, the plain and per-token-scaled fp8
+    stores ("fp8", "fp8_scaled") and fp16 queries over "fp8_block".
     """
 
     def __init__(
@@ -2212,26 +2219,31 @@ class PagedMlaSession(PagedDecodeSession):
         group: dist.ProcessGroup | None = None,
         device: torch.device | str = "cuda",
     ) -> None:
-        from .ops.flash import MLA_D_QK
+        from .ops.flash import MLA_D_QK, MLA_FP8_ROW
 
         if page not in _PAGE_SIZES:
             raise ValueError(f"PagedMlaSession: page must be one of "
                              f"{_PAGE_SIZES}, got {page!r}")
+        self.fp8_block = isinstance(dtype, str) and dtype == "fp8_block"
         td = _DTYPES.get(dtype, dtype) if isinstance(dtype, str) else dtype
         if td == torch.float8_e4m3fn or dtype == "fp8_scaled":
             raise NotImplementedError(
-                "PagedMlaSession: an fp8 latent store is not implemented; "
-                "use bf16 or fp16")
-        if td not in (torch.bfloat16, torch.float16):
-            raise ValueError(f"PagedMlaSession: dtype must be bf16 or fp16, "
-                             f"got {dtype!r}")
+                "PagedMlaSession: the plain and per-token-scaled fp8 stores "
+                "are not implemented for the latent pool; use "
+                "dtype='fp8_block', bf16 or fp16")
+        if self.fp8_block:
+            td = torch.uint8
+        elif td not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"PagedMlaSession: dtype must be bf16, fp16 or "
+                             f"'fp8_block', got {dtype!r}")
         _, local_cap = self._setup(batch, max_tokens, device, td, block, group)
         self._page = page
         max_pages = (local_cap + page - 1) // page
         if n_pages is None:
             n_pages = batch * max_pages
-        self.pool = _zeroed((max(1, n_pages), 1, page, MLA_D_QK), td,
-                            self.device)
+        self.pool = _zeroed(
+            (max(1, n_pages), 1, page,
+             MLA_FP8_ROW if self.fp8_block else MLA_D_QK), td, self.device)
         # one payload: the parent's K / V bookkeeping sees the same tensor
         self.k_pool = self.v_pool = self.pool
         self._alloc_scales(self.pool)
@@ -2250,21 +2262,40 @@ class PagedMlaSession(PagedDecodeSession):
             off = pos % self._page
             m = min(n - t, self._page - off)
             pid = self._pages[b][pos // self._page]
-            self.pool[pid, :, off : off + m] = \
-                k_rows[:, t : t + m].to(self.pool.dtype)
+            rows = k_rows[:, t : t + m].to(self._row_dtype)
+            if self.fp8_block:   # on the host: the oracle's own bytes
+                rows = quantize_mla_fp8(rows.cpu()).to(self.device)
+            self.pool[pid, :, off : off + m] = rows
             t, pos = t + m, pos + m
 
+    @property
+    def _row_dtype(self) -> torch.dtype:
+        """What the caller's (.., 576) rows are cast to before they are
+        stored: the pool's dtype, or bf16 ahead of the fp8_block quantizer."""
+        return torch.bfloat16 if self.fp8_block else self.pool.dtype
+
     def _launch_append_n(self, ext, k_new, v_new, counts_dev, vis_dev) -> None:
-        ext.mla_pool_append(
-            self.pool, self.page_table,
-            k_new.to(self.pool.dtype).contiguous(), self.total_dev,
-            self.local_len_dev, counts_dev, vis_dev, self.block, self.rank,
-            self.world)
+        append = ext.mla_pool_append_quant if self.fp8_block \
+            else ext.mla_pool_append
+        append(self.pool, self.page_table,
+               k_new.to(self._row_dtype).contiguous(), self.total_dev,
+               self.local_len_dev, counts_dev, vis_dev, self.block, self.rank,
+               self.world)
+
+    def _check_many(self, k_new: torch.Tensor, v_new: torch.Tensor,
+                    who: str = "append_many") -> int:
+        if not self.fp8_block:
+            return super()._check_many(k_new, v_new, who)
+        # _latent() has checked the rows, whose width is not the store's
+        if not 1 <= k_new.shape[2] <= 16:
+            raise ValueError(f"{who}: T must be in 1..16, got "
+                             f"{k_new.shape[2]}")
+        return k_new.shape[2]
 
     # ---- cache updates ----
     def _latent(self, c: torch.Tensor, who: str) -> torch.Tensor:
         if c.dim() != 4 or c.shape[0] != self.batch or c.shape[1] != 1 \
-                or c.shape[3] != self.pool.size(3):
+                or c.shape[3] != 576:
             raise ValueError(
                 f"{who}: the new rows must be (B, 1, T, 576) with B = "
                 f"{self.batch}, got {tuple(c.shape)}")
@@ -2346,12 +2377,17 @@ class PagedMlaSession(PagedDecodeSession):
             raise ValueError("graphed_step needs a GPU session")
         c_static = self._latent(c_static, "graphed_step")
         if (q_static.dim() != 4 or q_static.shape[2] != 1
-                or c_static.shape[2] != 1 or c_static.dtype != self.pool.dtype
+                or c_static.shape[2] != 1 or c_static.dtype != self._row_dtype
                 or not c_static.is_contiguous()):
             raise ValueError(
                 "graphed_step: q_static is (B, Hq, 1, 576) and c_static a "
-                "contiguous (B, 1, 1, 576) tensor of the pool's dtype")
+                "contiguous (B, 1, 1, 576) tensor of the pool's dtype (bf16 "
+                "under 'fp8_block')")
         ext = self._ext()
+        append, decode = (
+            (ext.mla_pool_append_quant, ext.flash_attention_mla_paged_fp8)
+            if self.fp8_block
+            else (ext.mla_pool_append, ext.flash_attention_mla_paged))
         counts_dev = torch.zeros(self.batch, dtype=torch.int32,
                                  device=self.device)
         vis_dev = self._vis_dev(1)
@@ -2359,13 +2395,11 @@ class PagedMlaSession(PagedDecodeSession):
                       else 1.0 / math.sqrt(q_static.shape[-1]))
 
         def step():
-            ext.mla_pool_append(self.pool, self.page_table, c_static,
-                                self.total_dev, self.local_len_dev,
-                                counts_dev, vis_dev, self.block, self.rank,
-                                self.world)
-            return ext.flash_attention_mla_paged(
-                q_static, self.pool, self.page_table, self.local_len_dev,
-                None, scale, 0)
+            append(self.pool, self.page_table, c_static, self.total_dev,
+                   self.local_len_dev, counts_dev, vis_dev, self.block,
+                   self.rank, self.world)
+            return decode(q_static, self.pool, self.page_table,
+                          self.local_len_dev, None, scale, 0)
 
         # the warm-up runs under all-zero counts, so no length moves
         graph, (out_l, lse_l) = _capture(step)
