@@ -19,6 +19,8 @@ Public surface (reference parity, SURVEY.md §0 capability set):
     tree_mla_decode        the same, sharded along the sequence
     mla_decode_paged       the same partial over a paged latent pool, with
                            up to 16 query positions per row
+    mla_prefill_paged      chunked prefill over that pool: any number of
+                           query positions per row
     PagedMlaSession        the MLA serving loop over that pool
     TreeAttention          nn.Module wrapper
     TreeAttentionConfig    workload/runtime config
@@ -27,7 +29,7 @@ Public surface (reference parity, SURVEY.md §0 capability set):
 from .config import TreeAttentionConfig
 from .data import make_data
 from .ops.flash import (flash_res_lse, hip_available, local_attention,
-                        mla_decode, mla_decode_paged)
+                        mla_decode, mla_decode_paged, mla_prefill_paged)
 from .ops.reference import attention_reference
 from .parallel.combine import (
     combine_partials,
@@ -63,6 +65,7 @@ __all__ = [
     "make_data",
     "mla_decode",
     "mla_decode_paged",
+    "mla_prefill_paged",
     "setup",
     "tree_attention",
     "tree_combine",

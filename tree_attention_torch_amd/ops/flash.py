@@ -340,11 +340,45 @@ def mla_decode_paged(
     Returns out (B, Hq, Tq, 512) fp32 and lse (B, Hq, Tq) fp32; a query that
     sees no key has out = 0 and lse = -inf.
     """
-    who = "mla_decode_paged"
+    return _mla_paged("mla_decode_paged", False, q, pool, page_table,
+                      kv_lens, vis, softmax_scale, splits)
+
+
+def mla_prefill_paged(
+    q: torch.Tensor,
+    pool: torch.Tensor,
+    page_table: torch.Tensor,
+    kv_lens: torch.Tensor,
+    vis: torch.Tensor | None = None,
+    softmax_scale: float | None = None,
+    splits: int = 0,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """MLA chunked prefill over a PAGED latent pool: mla_decode_paged's
+    arguments, masks and results for ANY number T >= 1 of query positions per
+    row, q (B, Hq, T, 576), e.g. the T new tokens of a prompt whose prefix the
+    pool already holds (vis=None: the chain mask over the row's last T rows).
+
+    On the GPU this is fa_mla_prefill_kernel: blocks of 64 (position, head)
+    rows that stream the pool once per block, where a loop of mla_decode_paged
+    streams it once per 16 positions: 1.3x - 5.3x faster than that loop at T
+    256 and 2048 behind 8K and 32K (profiles/README.md, "MLA chunked
+    prefill"). mla_decode_paged is never routed here. The "fp8_block" pool
+    works on the CPU and raises NotImplementedError on the GPU.
+    """
+    return _mla_paged("mla_prefill_paged", True, q, pool, page_table, kv_lens,
+                      vis, softmax_scale, splits)
+
+
+def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
+               splits):
+    """What mla_decode_paged (the decode kernel, Tq <= MLA_MAX_TQ) and
+    mla_prefill_paged (prefill=True: the prefill kernel, any Tq) share."""
     if q.dim() != 4 or q.shape[-1] != MLA_D_QK:
         raise ValueError(f"{who}: q is (B, Hq, Tq, {MLA_D_QK})")
     b, hq, tq = q.shape[:3]
-    if not 1 <= tq <= MLA_MAX_TQ:
+    if prefill and tq < 1:
+        raise ValueError(f"{who}: Tq = {tq}; at least one query position")
+    if not prefill and not 1 <= tq <= MLA_MAX_TQ:
         raise ValueError(f"{who}: Tq = {tq} is outside 1..{MLA_MAX_TQ}")
     if not 1 <= hq <= MLA_MAX_HEADS:
         raise ValueError(
@@ -376,7 +410,7 @@ def mla_decode_paged(
         softmax_scale = 1.0 / math.sqrt(MLA_D_QK)
     kv_lens = kv_lens.to(device=q.device, dtype=torch.int64).contiguous()
     if vis is None:
-        vis = mla_chain_vis(kv_lens, tq) if tq > 1 else None
+        vis = mla_chain_vis(kv_lens, tq) if tq > 1 or prefill else None
     else:
         vis = vis.to(device=q.device, dtype=torch.int64).contiguous()
     if q.device.type != "cuda":
@@ -397,12 +431,20 @@ def mla_decode_paged(
             f"{who}: the gfx950 HIP extension _tree_attn_hip is not built "
             "but a GPU tensor was passed. Build it with "
             f"__graft_entry__.build(). Import error: {_EXT_ERR}")
+    if fp8 and prefill:
+        raise NotImplementedError(
+            f"{who}: no chunked prefill over the fp8_block pool on the GPU; "
+            "loop mla_decode_paged, or use a bf16 or fp16 pool")
     if fp8:
         return ext.flash_attention_mla_paged_fp8(
             q.contiguous(), pool, page_table, kv_lens, vis,
             float(softmax_scale), int(splits or 0))
     if q.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(f"{who}: q and pool must both be bf16 or both fp16")
+    if prefill:
+        return ext.flash_attention_mla_prefill_paged(
+            q.contiguous(), pool, page_table, kv_lens, vis,
+            float(softmax_scale), int(splits or 0))
     return ext.flash_attention_mla_paged(
         q.contiguous(), pool, page_table, kv_lens, vis, float(softmax_scale),
         int(splits or 0))
@@ -421,4 +463,5 @@ def flash_res_lse(
 
 __all__ = ["local_attention", "local_attention_mx", "flash_res_lse",
            "hip_available", "decode_loop_chunks", "mla_decode",
-           "mla_decode_paged", "mla_chain_vis", "MLA_FP8_ROW"]
+           "mla_decode_paged", "mla_prefill_paged", "mla_chain_vis",
+           "MLA_FP8_ROW"]

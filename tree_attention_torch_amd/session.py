@@ -2175,7 +2175,7 @@ def _mla_unsupported(what: str):
         raise NotImplementedError(
             f"PagedMlaSession: {what} is not implemented for the MLA latent "
             "pool (prefill, append, attend, append_many, attend_many, "
-            "truncate, reset and graphed_step are)")
+            "attend_prefill, truncate, reset and graphed_step are)")
     return refuse
 
 
@@ -2203,9 +2203,12 @@ class PagedMlaSession(PagedDecodeSession):
     append_many / attend_many / truncate with up to 16 drafts per row; the
     drafts share the latent rows, so they are more MFMA rows of the same KV
     stream. graphed_step() captures append kernel, decode kernel and split
-    combine. Not implemented: fork, tree drafts, shared-prefix decode,
-    attend_prefill, graphed_step_many, the plain and per-token-scaled fp8
-    stores ("fp8", "fp8_scaled") and fp16 queries over "fp8_block".
+    combine. attend_prefill() takes the queries of the last T tokens of one
+    row, any T, through the 64-row prefill kernel (bf16 and fp16 pools).
+    Not implemented: fork, tree drafts, shared-prefix decode,
+    graphed_step_many, the plain and per-token-scaled fp8 stores ("fp8",
+    "fp8_scaled"), fp16 queries and attend_prefill on the GPU over
+    "fp8_block".
     """
 
     def __init__(
@@ -2422,11 +2425,53 @@ class PagedMlaSession(PagedDecodeSession):
 
         return replay
 
+    def attend_prefill(self, b: int, q: torch.Tensor,
+                       softmax_scale: float | None = None,
+                       combine: str = "auto") -> torch.Tensor:
+        """Chunked prefill: q (Hq, T, 576) or (1, Hq, T, 576) holds the
+        queries of the LAST T tokens row b holds (prefill(b, c_seq) first);
+        query i attends global positions <= totals[b] - T + i, where they lie
+        in the pool -> (1, Hq, T, 512) fp32. One row per call, not graphed;
+        no length or page is touched. On the GPU this is
+        fa_mla_prefill_kernel (ops.flash.mla_prefill_paged); an "fp8_block"
+        session raises NotImplementedError there."""
+        from .ops.flash import mla_prefill_paged
+
+        if not 0 <= b < self.batch:
+            raise ValueError(f"attend_prefill: b = {b} is outside "
+                             f"[0, {self.batch})")
+        if q.dim() == 3:
+            q = q[None]
+        if (q.dim() != 4 or q.shape[0] != 1 or q.shape[2] < 1
+                or q.shape[3] != 576):
+            raise ValueError(
+                f"attend_prefill: q must be (Hq, T, 576) or (1, Hq, T, 576) "
+                f"with T >= 1, got {tuple(q.shape)}")
+        t = q.shape[2]
+        if t > self.totals[b]:
+            raise ValueError(
+                f"attend_prefill: row {b} holds {self.totals[b]} tokens, "
+                f"fewer than the {t} queries")
+        if self.fp8_block and q.device.type == "cuda":
+            raise NotImplementedError(
+                "PagedMlaSession.attend_prefill: no chunked prefill over the "
+                "fp8_block pool on the GPU; use a bf16 or fp16 session")
+        if self.local_lens[b] == 0:   # no local key: the empty partial
+            out_l = q.new_zeros((1, q.shape[1], t, 512), dtype=torch.float32)
+            lse_l = q.new_full((1, q.shape[1], t), float("-inf"),
+                               dtype=torch.float32)
+        else:
+            out_l, lse_l = mla_prefill_paged(
+                q, self.pool, self.page_table[b : b + 1],
+                self.local_len_dev[b : b + 1],
+                self._prefill_vis(b, t)[None].to(self.device), softmax_scale)
+        out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
+        return out
+
     fork = _mla_unsupported("fork")
     append_tree = _mla_unsupported("append_tree (tree drafts)")
     attend_tree = _mla_unsupported("attend_tree (tree drafts)")
     commit = _mla_unsupported("commit (tree drafts)")
     graphed_step_tree = _mla_unsupported("graphed_step_tree (tree drafts)")
     graphed_step_many = _mla_unsupported("graphed_step_many")
-    attend_prefill = _mla_unsupported("attend_prefill")
     shared_plan = _mla_unsupported("shared-prefix decode (shared_plan)")
