@@ -321,6 +321,7 @@ def mla_decode_paged(
     vis: torch.Tensor | None = None,
     softmax_scale: float | None = None,
     splits: int = 0,
+    tree: tuple[torch.Tensor, torch.Tensor] | None = None,
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """MLA decode partial over a PAGED latent pool, Tq query positions per
     row (a multi-token verify step).
@@ -337,11 +338,34 @@ def mla_decode_paged(
     min(vis[b, i], kv_lens[b]); None is the chain mask mla_chain_vis. splits
     forces the split-KV count (0: the plan).
 
+    tree = (base, mask), instead of vis, is the ancestor mask of a verify
+    step over a draft TREE (ops/hip/ta_abi.h TreeArgs): base (B,) int64 is
+    the length of row b's committed prefix and mask (B, Tq) int32, both on
+    q's device; the key at position p is masked for query i iff p >= base[b]
+    and bit p - base[b] of mask[b, i] is clear (the drafts are the at most 16
+    rows behind the prefix; higher bits are ignored).
+    PagedMlaSession.append_tree leaves both.
+
     Returns out (B, Hq, Tq, 512) fp32 and lse (B, Hq, Tq) fp32; a query that
     sees no key has out = 0 and lse = -inf.
     """
+    if tree is not None:
+        if vis is not None:
+            raise ValueError("mla_decode_paged: vis and tree exclude each "
+                             "other")
+        base, mask = tree
+        b, tq = q.shape[0], q.shape[2] if q.dim() == 4 else 0
+        if (tuple(base.shape) != (b,) or base.dtype != torch.int64
+                or tuple(mask.shape) != (b, tq) or mask.dtype != torch.int32
+                or base.device != q.device or mask.device != q.device):
+            raise ValueError(
+                f"mla_decode_paged: tree is (base (B,) int64, mask (B, Tq) "
+                f"int32) = (({b},), ({b}, {tq})) on q's device, got "
+                f"{tuple(base.shape)} {base.dtype} / {tuple(mask.shape)} "
+                f"{mask.dtype}")
+        tree = (base.contiguous(), mask.contiguous())
     return _mla_paged("mla_decode_paged", False, q, pool, page_table,
-                      kv_lens, vis, softmax_scale, splits)
+                      kv_lens, vis, softmax_scale, splits, tree)
 
 
 def mla_prefill_paged(
@@ -370,9 +394,10 @@ def mla_prefill_paged(
 
 
 def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
-               splits):
+               splits, tree=None):
     """What mla_decode_paged (the decode kernel, Tq <= MLA_MAX_TQ) and
-    mla_prefill_paged (prefill=True: the prefill kernel, any Tq) share."""
+    mla_prefill_paged (prefill=True: the prefill kernel, any Tq) share.
+    tree: the checked (base, mask) of mla_decode_paged, instead of vis."""
     if q.dim() != 4 or q.shape[-1] != MLA_D_QK:
         raise ValueError(f"{who}: q is (B, Hq, Tq, {MLA_D_QK})")
     b, hq, tq = q.shape[:3]
@@ -409,7 +434,9 @@ def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(MLA_D_QK)
     kv_lens = kv_lens.to(device=q.device, dtype=torch.int64).contiguous()
-    if vis is None:
+    if tree is not None:
+        pass
+    elif vis is None:
         vis = mla_chain_vis(kv_lens, tq) if tq > 1 or prefill else None
     else:
         vis = vis.to(device=q.device, dtype=torch.int64).contiguous()
@@ -424,7 +451,7 @@ def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
             rows = pool[ids, 0].reshape(-1, pool.shape[3])[:n]
             ckv[i, 0, :n] = dequantize_mla_fp8(rows) if fp8 else rows
         return reference.mla_reference(q.float() if fp8 else q, ckv, lens,
-                                       softmax_scale, vis=vis)
+                                       softmax_scale, vis=vis, tree=tree)
     ext = _load_extension()
     if ext is None:
         raise RuntimeError(
@@ -435,12 +462,17 @@ def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
         raise NotImplementedError(
             f"{who}: no chunked prefill over the fp8_block pool on the GPU; "
             "loop mla_decode_paged, or use a bf16 or fp16 pool")
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{who}: q and pool must both be bf16 or both fp16")
+    if tree is not None:
+        decode = ext.flash_attention_mla_paged_tree_fp8 if fp8 \
+            else ext.flash_attention_mla_paged_tree
+        return decode(q.contiguous(), pool, page_table, kv_lens, *tree,
+                      float(softmax_scale), int(splits or 0))
     if fp8:
         return ext.flash_attention_mla_paged_fp8(
             q.contiguous(), pool, page_table, kv_lens, vis,
             float(softmax_scale), int(splits or 0))
-    if q.dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError(f"{who}: q and pool must both be bf16 or both fp16")
     if prefill:
         return ext.flash_attention_mla_prefill_paged(
             q.contiguous(), pool, page_table, kv_lens, vis,

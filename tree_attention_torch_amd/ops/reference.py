@@ -115,6 +115,7 @@ def mla_reference(
     softmax_scale: float | None = None,
     d_v: int = 512,
     vis: torch.Tensor | None = None,
+    tree: tuple[torch.Tensor, torch.Tensor] | None = None,
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """fp32 oracle of the MLA decode partial (ops/flash.py::mla_decode).
 
@@ -123,6 +124,9 @@ def mla_reference(
     past each batch row's length (they may hold anything, NaN included).
     vis (B, Tq) masks, for query position t of row b, the keys at or past
     vis[b, t] as well (the verify step's per-query-row visible lengths).
+    tree = (base (B,), mask (B, Tq)) masks the key at position p >= base[b]
+    unless bit p - base[b] of mask[b, t] is set (bits above 15 are ignored):
+    the ancestor mask of a draft tree.
     Returns out (B, Hq, Tq, d_v) and lse (B, Hq, Tq); a row with no key has
     out = 0 and lse = -inf.
     """
@@ -139,6 +143,13 @@ def mla_reference(
     if vis is not None:
         pos = torch.arange(ckv.shape[2], device=ckv.device)
         unseen = pos[None, None, :] >= vis.to(ckv.device)[:, :, None]
+        scores = scores.masked_fill(unseen[:, None], float("-inf"))
+    if tree is not None:
+        base, mask = (x.to(ckv.device).long() for x in tree)
+        slot = torch.arange(ckv.shape[2], device=ckv.device)[None, :] \
+            - base[:, None]                                   # (B, Tkv)
+        bit = (mask[:, :, None] >> slot.clamp(0, 16)[:, None, :]) & 1
+        unseen = (slot >= 0)[:, None, :] & ((bit == 0) | (slot >= 16)[:, None, :])
         scores = scores.masked_fill(unseen[:, None], float("-inf"))
     lse = torch.logsumexp(scores, dim=-1)
     m = scores.amax(dim=-1, keepdim=True)

@@ -2175,7 +2175,8 @@ def _mla_unsupported(what: str):
         raise NotImplementedError(
             f"PagedMlaSession: {what} is not implemented for the MLA latent "
             "pool (prefill, append, attend, append_many, attend_many, "
-            "attend_prefill, truncate, reset and graphed_step are)")
+            "append_tree, attend_tree, commit, attend_prefill, truncate, "
+            "reset, graphed_step and graphed_step_tree are)")
     return refuse
 
 
@@ -2202,11 +2203,16 @@ class PagedMlaSession(PagedDecodeSession):
     (the multi-token-prediction heads of the models that use MLA) is
     append_many / attend_many / truncate with up to 16 drafts per row; the
     drafts share the latent rows, so they are more MFMA rows of the same KV
-    stream. graphed_step() captures append kernel, decode kernel and split
-    combine. attend_prefill() takes the queries of the last T tokens of one
-    row, any T, through the 64-row prefill kernel (bf16 and fp16 pools).
-    Not implemented: fork, tree drafts, shared-prefix decode,
-    graphed_step_many, the plain and per-token-scaled fp8 stores ("fp8",
+    stream. A draft TREE is append_tree / attend_tree / commit with up to 16
+    nodes per row, on every store, sharded or not: the append kernel turns the
+    parents into one ancestor mask per node, the decode kernel keeps a row's
+    mask in one register, commit re-stores the accepted path from the kept
+    drafts and hands back the pages only rejected drafts held.
+    graphed_step() captures append kernel, decode kernel and split combine,
+    graphed_step_tree() the same chain for a tree step. attend_prefill()
+    takes the queries of the last T tokens of one row, any T, through the
+    64-row prefill kernel (bf16 and fp16 pools).
+    Not implemented: fork, shared-prefix decode, graphed_step_many, the plain and per-token-scaled fp8 stores ("fp8",
     "fp8_scaled"), fp16 queries and attend_prefill on the GPU over
     "fp8_block".
     """
@@ -2468,10 +2474,132 @@ class PagedMlaSession(PagedDecodeSession):
         out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
         return out
 
+    # ---- tree-shaped drafts: the parent's bookkeeping (append_tree's
+    # validation and reserve, attend_tree, commit and its page release) over
+    # one latent tensor; only the launches and the partial are the pool's ----
+    def _cast_new(self, k_new: torch.Tensor, v_new: torch.Tensor):
+        c = k_new.to(self._row_dtype).contiguous()
+        return c, c
+
+    def _launch_append_tree(self, ext, k_new, v_new, counts_dev, parents_dev,
+                            base_dev, mask_dev) -> None:
+        append = ext.mla_pool_append_tree_quant if self.fp8_block \
+            else ext.mla_pool_append_tree
+        append(self.pool, self.page_table, k_new, self.total_dev,
+               self.local_len_dev, counts_dev, parents_dev, base_dev,
+               mask_dev, self.block, self.rank, self.world)
+
+    def _launch_attend_tree(self, ext, q, scale: float, base_dev, mask_dev):
+        decode = ext.flash_attention_mla_paged_tree_fp8 if self.fp8_block \
+            else ext.flash_attention_mla_paged_tree
+        return decode(q.contiguous(), self.pool, self.page_table,
+                      self.local_len_dev, base_dev, mask_dev, scale, 0)
+
+    def _launch_commit(self, ext, k_new, v_new, counts_dev, path_dev,
+                       lens_dev) -> None:
+        commit = ext.mla_pool_commit_path_quant if self.fp8_block \
+            else ext.mla_pool_commit_path
+        commit(self.pool, self.page_table, k_new, self.total_dev,
+               self.local_len_dev, counts_dev, path_dev, lens_dev, self.block,
+               self.rank, self.world)
+
+    def _local_partial_tree(self, q: torch.Tensor, tree: dict,
+                            softmax_scale: float | None):
+        # the kernel on the GPU, the eager masked softmax on the CPU, both
+        # under the base / mask buffers append_tree has filled
+        from .ops.flash import mla_decode_paged
+
+        return mla_decode_paged(q, self.pool, self.page_table,
+                                self.local_len_dev, None, softmax_scale,
+                                tree=self._tree_dev(tree["t"]))
+
+    def append_tree(self, c_new: torch.Tensor, parents, counts=None) -> None:
+        """Append up to T draft NODES of a token tree per sequence, (B, 1, T,
+        576) in topological order, with ``parents`` and ``counts`` as
+        PagedDecodeSession.append_tree takes them. attend_tree(q) with q (B,
+        Hq, T, 576) then verifies every node against the committed rows, the
+        node itself and its ancestors, and commit(paths, lens) keeps the
+        accepted root-to-node path and hands back the pages only rejected
+        drafts held; under "fp8_block" it quantizes the kept bf16 drafts
+        again, so the committed bytes are quantize_mla_fp8's."""
+        c_new = self._latent(c_new, "append_tree")
+        super().append_tree(c_new, c_new, parents, counts)
+
+    def graphed_step_tree(self, q_static: torch.Tensor,
+                          c_static: torch.Tensor,
+                          parents_static: torch.Tensor,
+                          softmax_scale: float | None = None,
+                          combine: str = "auto"):
+        """graphed_step for a tree of T draft nodes per row: the tree append
+        kernel, the ancestor-mask decode kernel and the split combine, one
+        linear chain, captured under an all-zero ``counts``. Returns
+        ``replay``.
+
+        Write the queries (B, Hq, T, 576), the nodes' rows (B, 1, T, 576)
+        and their parents (B, T) int32 into the static tensors, then
+        ``replay(counts=None)`` reserves, advances the mirror, refreshes the
+        static counts, replays and leaves the step as the pending tree.
+        commit() after a replay is an eager launch that reads c_static: call
+        it before the next step's rows are written."""
+        if self.device.type != "cuda":
+            raise ValueError("graphed_step needs a GPU session")
+        c_static = self._latent(c_static, "graphed_step_tree")
+        t = self._check_many(c_static, c_static, "graphed_step_tree")
+        if (q_static.dim() != 4 or q_static.shape[0] != self.batch
+                or q_static.shape[2] != t or q_static.shape[3] != 576
+                or c_static.dtype != self._row_dtype
+                or not c_static.is_contiguous()):
+            raise ValueError(
+                f"graphed_step_tree: q_static is (B, Hq, T, 576) with B = "
+                f"{self.batch} and the T = {t} of c_static, a contiguous (B, "
+                f"1, T, 576) tensor of the pool's dtype (bf16 under "
+                f"'fp8_block'); got {tuple(q_static.shape)}")
+        if not isinstance(parents_static, torch.Tensor):
+            raise ValueError("graphed_step_tree: parents_static must be a "
+                             "(B, T) int32 device tensor")
+        parents_dev, _ = self._node_table("graphed_step_tree",
+                                          "parents_static", parents_static, t,
+                                          None)
+        if parents_dev is not parents_static:
+            raise ValueError("graphed_step_tree: parents_static must be "
+                             "contiguous")
+        ext = self._ext()
+        counts_dev = torch.zeros(self.batch, dtype=torch.int32,
+                                 device=self.device)
+        base_dev, mask_dev = self._tree_dev(t)
+        scale = _scale(softmax_scale, q_static)
+
+        def step():
+            self._launch_append_tree(ext, c_static, c_static, counts_dev,
+                                     parents_dev, base_dev, mask_dev)
+            return self._launch_attend_tree(ext, q_static, scale, base_dev,
+                                            mask_dev)
+
+        # the warm-up runs under all-zero counts, so no length moves; it
+        # does rewrite the shared base / mask buffers of this T, so a tree
+        # pending from an eager append_tree ends here
+        self._tree = None
+        graph, (out_l, lse_l) = _capture(step)
+        self._graph_tree = graph  # keep alive
+        in_buffer = [[0] * self.batch]   # what counts_dev holds now
+
+        def replay(counts=None) -> torch.Tensor:
+            counts = self._counts(counts, t)
+            self._reserve(self._many_ends(counts))
+            self._advance_tree(counts, t, c_static, c_static, parents_dev,
+                               None)
+            if counts != in_buffer[0]:
+                counts_dev.copy_(self._counts_dev(counts))
+                in_buffer[0] = counts
+            graph.replay()
+            if self.world == 1:
+                return out_l
+            out, _ = tree_combine(out_l, lse_l, strategy=combine,
+                                  group=self.group)
+            return out
+
+        return replay
+
     fork = _mla_unsupported("fork")
-    append_tree = _mla_unsupported("append_tree (tree drafts)")
-    attend_tree = _mla_unsupported("attend_tree (tree drafts)")
-    commit = _mla_unsupported("commit (tree drafts)")
-    graphed_step_tree = _mla_unsupported("graphed_step_tree (tree drafts)")
     graphed_step_many = _mla_unsupported("graphed_step_many")
     shared_plan = _mla_unsupported("shared-prefix decode (shared_plan)")
