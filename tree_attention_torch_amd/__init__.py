@@ -20,7 +20,8 @@ Public surface (reference parity, SURVEY.md §0 capability set):
     mla_decode_paged       the same partial over a paged latent pool, with
                            up to 16 query positions per row
     mla_prefill_paged      chunked prefill over that pool: any number of
-                           query positions per row
+                           query positions per row; compute="fp8" runs
+                           the fp8_block pool on e4m3 MFMA operands
     PagedMlaSession        the MLA serving loop over that pool
     TreeAttention          nn.Module wrapper
     TreeAttentionConfig    workload/runtime config

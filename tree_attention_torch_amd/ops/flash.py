@@ -20,7 +20,7 @@ import os
 import torch
 
 from . import reference
-from ..quant import MLA_FP8_ROW, dequantize_mla_fp8
+from ..quant import MLA_FP8_ROW, dequantize_mla_fp8, quantize_mla_fp8
 
 _EXT = None
 _EXT_ERR: Exception | None = None
@@ -376,6 +376,7 @@ def mla_prefill_paged(
     vis: torch.Tensor | None = None,
     softmax_scale: float | None = None,
     splits: int = 0,
+    compute: str | None = None,
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """MLA chunked prefill over a PAGED latent pool: mla_decode_paged's
     arguments, masks and results for ANY number T >= 1 of query positions per
@@ -386,18 +387,34 @@ def mla_prefill_paged(
     rows that stream the pool once per block, where a loop of mla_decode_paged
     streams it once per 16 positions: 1.3x - 5.3x faster than that loop at T
     256 and 2048 behind 8K and 32K (profiles/README.md, "MLA chunked
-    prefill"). mla_decode_paged is never routed here. The "fp8_block" pool
-    works on the CPU and raises NotImplementedError on the GPU.
+    prefill"). mla_decode_paged is never routed here.
+
+    compute="fp8" is the consent to run an "fp8_block" pool under a bf16 q on
+    the GPU, through fa_mla_prefill_fp8_kernel: the pool's e4m3 bytes enter
+    the fp8 MFMA as they lie, and the LATENT columns of q are rounded to e4m3
+    per (row, 128-column block) by quant.quantize_mla_fp8's rule; rotary
+    columns, P and V are as in mla_decode_paged's fp8_block path. On the CPU
+    it is that kernel's oracle: the fp32 reference over the dequantized rows
+    and dequantize_mla_fp8(quantize_mla_fp8(q)). The rounding costs up to
+    0.095 of out (abs err / (1 + abs ref)) and 0.067 of lse against unrounded
+    queries (README, "MLA fp8 latent store"). Without the keyword the
+    "fp8_block" pool works on the CPU and raises NotImplementedError on the
+    GPU. compute="fp8" over a bf16 or fp16 pool, and any other value, raise
+    ValueError.
     """
     return _mla_paged("mla_prefill_paged", True, q, pool, page_table, kv_lens,
-                      vis, softmax_scale, splits)
+                      vis, softmax_scale, splits, compute=compute)
 
 
 def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
-               splits, tree=None):
+               splits, tree=None, compute=None):
     """What mla_decode_paged (the decode kernel, Tq <= MLA_MAX_TQ) and
     mla_prefill_paged (prefill=True: the prefill kernel, any Tq) share.
-    tree: the checked (base, mask) of mla_decode_paged, instead of vis."""
+    tree: the checked (base, mask) of mla_decode_paged, instead of vis.
+    compute: mla_prefill_paged's keyword (prefill only)."""
+    if compute not in (None, "fp8"):
+        raise ValueError(f"{who}: compute must be None or 'fp8', got "
+                         f"{compute!r}")
     if q.dim() != 4 or q.shape[-1] != MLA_D_QK:
         raise ValueError(f"{who}: q is (B, Hq, Tq, {MLA_D_QK})")
     b, hq, tq = q.shape[:3]
@@ -423,6 +440,9 @@ def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
             f"takes a bf16 q (got {q.dtype})")
     if not fp8 and pool.dtype != q.dtype:
         raise ValueError(f"{who}: q and pool must have one dtype")
+    if compute == "fp8" and not fp8:
+        raise ValueError(f"{who}: compute='fp8' needs the fp8_block pool; a "
+                         f"{pool.dtype} pool holds nothing in e4m3")
     if (page_table.dim() != 2 or page_table.shape[0] != b
             or page_table.shape[1] < 1 or page_table.dtype != torch.int32):
         raise ValueError(f"{who}: page_table is int32 (B, max_pages)")
@@ -450,17 +470,21 @@ def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
             ids = page_table[i, : -(-n // page)].long().clamp(0, pool.shape[0] - 1)
             rows = pool[ids, 0].reshape(-1, pool.shape[3])[:n]
             ckv[i, 0, :n] = dequantize_mla_fp8(rows) if fp8 else rows
-        return reference.mla_reference(q.float() if fp8 else q, ckv, lens,
-                                       softmax_scale, vis=vis, tree=tree)
+        q_ref = q.float() if fp8 else q
+        if compute == "fp8":  # the kernel's rounding of the latent columns
+            q_ref = dequantize_mla_fp8(quantize_mla_fp8(q_ref))
+        return reference.mla_reference(q_ref, ckv, lens, softmax_scale,
+                                       vis=vis, tree=tree)
     ext = _load_extension()
     if ext is None:
         raise RuntimeError(
             f"{who}: the gfx950 HIP extension _tree_attn_hip is not built "
             "but a GPU tensor was passed. Build it with "
             f"__graft_entry__.build(). Import error: {_EXT_ERR}")
-    if fp8 and prefill:
+    if fp8 and prefill and compute != "fp8":
         raise NotImplementedError(
-            f"{who}: no chunked prefill over the fp8_block pool on the GPU; "
+            f"{who}: no chunked prefill over the fp8_block pool on the GPU "
+            "without compute='fp8', which rounds q's latent columns to e4m3; "
             "loop mla_decode_paged, or use a bf16 or fp16 pool")
     if q.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(f"{who}: q and pool must both be bf16 or both fp16")
@@ -469,6 +493,10 @@ def _mla_paged(who, prefill, q, pool, page_table, kv_lens, vis, softmax_scale,
             else ext.flash_attention_mla_paged_tree
         return decode(q.contiguous(), pool, page_table, kv_lens, *tree,
                       float(softmax_scale), int(splits or 0))
+    if fp8 and prefill:
+        return ext.flash_attention_mla_prefill_paged_fp8(
+            q.contiguous(), pool, page_table, kv_lens, vis,
+            float(softmax_scale), int(splits or 0))
     if fp8:
         return ext.flash_attention_mla_paged_fp8(
             q.contiguous(), pool, page_table, kv_lens, vis,

@@ -2433,16 +2433,27 @@ class PagedMlaSession(PagedDecodeSession):
 
     def attend_prefill(self, b: int, q: torch.Tensor,
                        softmax_scale: float | None = None,
-                       combine: str = "auto") -> torch.Tensor:
+                       combine: str = "auto",
+                       compute: str | None = None) -> torch.Tensor:
         """Chunked prefill: q (Hq, T, 576) or (1, Hq, T, 576) holds the
         queries of the LAST T tokens row b holds (prefill(b, c_seq) first);
         query i attends global positions <= totals[b] - T + i, where they lie
         in the pool -> (1, Hq, T, 512) fp32. One row per call, not graphed;
         no length or page is touched. On the GPU this is
         fa_mla_prefill_kernel (ops.flash.mla_prefill_paged); an "fp8_block"
-        session raises NotImplementedError there."""
+        session raises NotImplementedError there unless compute="fp8"
+        consents to rounding q's latent columns to e4m3
+        (fa_mla_prefill_fp8_kernel; mla_prefill_paged has the cost). On any
+        other session compute="fp8" raises ValueError."""
         from .ops.flash import mla_prefill_paged
 
+        if compute not in (None, "fp8"):
+            raise ValueError(f"attend_prefill: compute must be None or "
+                             f"'fp8', got {compute!r}")
+        if compute == "fp8" and not self.fp8_block:
+            raise ValueError(
+                "attend_prefill: compute='fp8' needs an fp8_block session; "
+                "this pool holds nothing in e4m3")
         if not 0 <= b < self.batch:
             raise ValueError(f"attend_prefill: b = {b} is outside "
                              f"[0, {self.batch})")
@@ -2458,10 +2469,11 @@ class PagedMlaSession(PagedDecodeSession):
             raise ValueError(
                 f"attend_prefill: row {b} holds {self.totals[b]} tokens, "
                 f"fewer than the {t} queries")
-        if self.fp8_block and q.device.type == "cuda":
+        if self.fp8_block and q.device.type == "cuda" and compute != "fp8":
             raise NotImplementedError(
                 "PagedMlaSession.attend_prefill: no chunked prefill over the "
-                "fp8_block pool on the GPU; use a bf16 or fp16 session")
+                "fp8_block pool on the GPU without compute='fp8'; use a bf16 "
+                "or fp16 session")
         if self.local_lens[b] == 0:   # no local key: the empty partial
             out_l = q.new_zeros((1, q.shape[1], t, 512), dtype=torch.float32)
             lse_l = q.new_full((1, q.shape[1], t), float("-inf"),
@@ -2470,7 +2482,8 @@ class PagedMlaSession(PagedDecodeSession):
             out_l, lse_l = mla_prefill_paged(
                 q, self.pool, self.page_table[b : b + 1],
                 self.local_len_dev[b : b + 1],
-                self._prefill_vis(b, t)[None].to(self.device), softmax_scale)
+                self._prefill_vis(b, t)[None].to(self.device), softmax_scale,
+                compute=compute)
         out, _ = tree_combine(out_l, lse_l, strategy=combine, group=self.group)
         return out
 
